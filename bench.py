@@ -13,6 +13,13 @@ single-row case is reported under "single_row".  Inputs are resident in HBM befo
 
     python bench.py [--gpus N --steps K --warmup W]            (N > 1: starts the N rank processes itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --dump-outputs DIR                     (the last timed step's results as DIR/<name>.npy: bench/dump.py)
+    python bench.py ... --full                                 (everything else the line can report: see below)
+
+A plain run sets up, warms up, times the K steps and prints the line: `value` (integrals per second of the timed steps),
+`ms_per_step`, the step's kernel times and its configuration.  --full adds, after the timed loop, the rooflines, the other
+Newton modes checked against the exact count on every pixel, the noisy step, mixed precision, reduced quadrature, single row
+and cone beam, the public NumPy boundary, the CPU baseline with its parity sample and (N > 1) every assembly mode.
 
 Multi-GPU: projection angles are sharded contiguously over the ranks (one process per GPU, RCCL).
   --scaling strong (default): the scan is FIXED - the metric's 1000 x 800 scan (or --workload config3: BASELINE
@@ -44,7 +51,7 @@ def main():
     import torch
     import torch.distributed as dist
     from dex_ct_sim_amd import matdecomp as md
-    from bench import modes, multi, roofline
+    from bench import multi
     from bench.step import Workload, mean
 
     wl = Workload(args, world, rank, local_rank)
@@ -69,9 +76,13 @@ def main():
     value = integrals_per_step / (elapsed / args.steps)
     sid_ms, gn_ms = mean(t_sid), mean(t_gn)
     gstats = md.last_gn_stats()             # of the last timed step's launches (the default mode)
+    dumped = None
+    if args.dump_outputs:                   # (N = 1: launch.parse) the last timed step's results, before anything else runs
+        from bench import dump
+        dumped = dump.write(wl, args.dump_outputs)
 
     multi_gpu = None
-    if world > 1:
+    if world > 1 and args.full:
         multi_gpu = multi.measure(wl, args, backend, chosen, auto, ms_per_step, t_sid, t_gn, t_exposed, integrals_per_step)
     if rank != 0:
         if world > 1:
@@ -108,9 +119,26 @@ def main():
         'siddon_only_integrals_per_s': n_rays * sum(n_e_spec) / (sid_ms * 1e-3),
         'siddon_rays_per_s': n_rays / (sid_ms * 1e-3),
         'gn_pixel_solves_per_s': n_rays / (gn_ms * 1e-3),
+        'full': args.full,
     }
     if multi_gpu is not None:
         out['multi_gpu'] = multi_gpu
+    if dumped is not None:
+        out['dumped_outputs'] = dumped
+    if args.full:
+        full(args, wl, out, world, precision, rows, n_rays, sid_ms, gn_ms, gstats, masked, gate_prep_s, integrals_per_step,
+             ms_per_step)
+    print(json.dumps(out))
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full(args, wl, out, world, precision, rows, n_rays, sid_ms, gn_ms, gstats, masked, gate_prep_s, integrals_per_step,
+         ms_per_step):
+    """--full: what the line reports beside the headline (rank 0, after the timed loop)."""
+    from dex_ct_sim_amd import matdecomp as md
+    from bench import modes, roofline
+    n = wl.n
 
     # ---- rooflines (bench/roofline.py).  The step's dominant kernel is the Newton launch (FP64 vector issue); the traversal
     # kernel is stated against the bound its counters show.  Integer geometry (segment counts) from the oracle's plan.
@@ -146,9 +174,6 @@ def main():
         out['cpu_baseline'] = None
     elif not args.no_cpu_baseline:
         cpu.cpu_baseline(wl, args, out)
-    print(json.dumps(out))
-    if world > 1:
-        dist.destroy_process_group()
 
 
 if __name__ == '__main__':

@@ -9,6 +9,9 @@ argument parser + orchestration; what it runs lives here, one concern per module
     roofline.py  the `roofline` / `roofline_siddon` objects
     dropin.py    the public NumPy boundary, wall-clock
     cpu.py       `cpu_baseline` + the parity sample - the only module that touches oracle/
+    dump.py      --dump-outputs: the last timed step's results as .npy files
+multi.measure, modes, roofline, dropin and cpu run only with --full; a plain run sets up, warms up, times the steps, dumps its
+outputs if asked and prints the line.
 """
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: 8.0 TB/s spec
 FP64_VALU_PEAK_TFLOPS = 78.6   # vector FP64

@@ -46,7 +46,19 @@ def parse(argv=None):
     ap.add_argument('--skip-gn-full-loop', action='store_true',
                     help='omit the extra full-loop Newton launch (keeps rocprof per-kernel averages clean)')
     ap.add_argument('--skip-noisy', action='store_true', help='omit the noisy step (quantum noise: the reference\'s dose-scaled mode)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything the line reports beside the headline: rooflines, the other Newton '
+                         'modes against the exact count, the noisy step, mixed precision, reduced quadrature, single row and cone '
+                         'beam, the public NumPy boundary, the CPU baseline and (N > 1) every assembly mode (the --skip-* / '
+                         '--no-cpu-baseline options leave parts of it out).  Without it the run sets up, warms up, times the '
+                         'steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed as DIR/<name>.npy (bench/dump.py; N = 1)')
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.dump_outputs and args.gpus > 1:
+        ap.error('--dump-outputs writes the outputs of one GPU\'s step: use it with --gpus 1')
     dv, dc = {'config2': (1000, 800), 'config3': (2000, 1024)}[args.workload]
     args.views = args.views or dv
     args.channels = args.channels or dc

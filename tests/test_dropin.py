@@ -32,9 +32,9 @@ print(get_sino.__module__, get_recon.__module__, get_basismat_sinos.__module__, 
 '''
 
 
-def test_reference_import_lines_resolve():
+def test_reference_import_lines_resolve(tmp_path):
     code = REFERENCE_IMPORTS % (DROPIN, os.path.join(INPUT, 'detector', 'eta_eid_mv.bin'))
-    out = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=300, cwd='/tmp')
+    out = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=300, cwd=tmp_path)
     assert out.returncode == 0, out.stderr[-2000:]
     mods = out.stdout.split()
     assert mods[:3] == ['dex_ct_sim_amd.forward_project', 'dex_ct_sim_amd.back_project', 'dex_ct_sim_amd.matdecomp']

@@ -124,9 +124,10 @@ def _load(name):
 def test_committed_screen_is_what_the_generator_produces():
     """The pixels left out of the live-pair comparison (ref_extra.npz: uns_raised, uns_ill) are exactly what the frozen
     criterion (make_goldens_r2.CRITERION_VERSION = 2) computes from the REAL reference on the committed inputs - so the
-    exclusion cannot be widened quietly after a kernel change.  Needs /root/reference (the build container); the
-    committed counts of the criterion are checked everywhere."""
-    import os
+    exclusion cannot be widened quietly after a kernel change.  The reference's answer to every call the screen makes
+    (optimize_sino_cpu on a pixel or on its ulp-shifted counts, raised or not) is stored in ref_screen_calls.npz
+    (make_goldens_screen.py, recorded from the real reference); the screen runs here on those answers, and a call the
+    reference was never asked fails the test."""
     import sys
     from conftest import GOLDEN
     e = _load('ref_extra.npz')
@@ -134,17 +135,25 @@ def test_committed_screen_is_what_the_generator_produces():
     assert int(e['uns_raised'].sum()) == 8 and int(e['uns_ill'].sum()) == 8 and e['uns_raised'].size == 192
     # criterion (2) of the frozen screen, recomputed from the committed arrays alone
     assert np.array_equal(e['uns_ill'] & ~e['uns_raised'] | ~(e['uns_cond'] <= 1e13) & ~e['uns_raised'], e['uns_ill'])
-    if not os.path.exists('/root/reference/matdecomp.py'):
-        pytest.skip('the reference is only present in the build container')
     sys.path.insert(0, GOLDEN)
-    import make_goldens
     import make_goldens_r2 as r2
     assert r2.CRITERION_VERSION == int(e['uns_criterion_version'])
-    ref = make_goldens.load_reference()
-    ref.xc.mixatten = make_goldens.load_pkg_module('xcompy').mixatten
+    rec = _load('ref_screen_calls.npz')
+    ee_fix, i0_fix, mus_fix = e['uns_ee'], e['uns_i0'], e['uns_mus']
+    answers = {(float(g0), float(g1), int(n)): (bool(r), a)
+               for (g0, g1), n, r, a in zip(rec['calls_g'], rec['calls_n_iters'], rec['calls_raised'], rec['calls_a'])}
+
+    def reference_answer(gp, ee, i0_1, mus, n_iters, verbose=False):
+        assert np.array_equal(ee, ee_fix) and np.array_equal(mus, mus_fix) and np.array_equal(i0_1[:, 0, :], i0_fix)
+        raised, a = answers[(float(gp[0, 0, 0]), float(gp[1, 0, 0]), int(n_iters))]
+        if raised:
+            raise np.linalg.LinAlgError('Singular matrix')
+        return a.reshape(1, 1, 2)
+
     # a third of the fixture's views keeps this at a few seconds; pixels are independent, so rows reproduce row by row
-    sel = slice(0, 2)
-    raised, raised_at, a50, ill, cond = r2.screen(ref.optimize_sino_cpu, e['uns_g'][:, sel], e['uns_ee'], e['uns_i0'],
+    sel = slice(*rec['views'])
+    assert (sel.start, sel.stop) == (0, 2)
+    raised, raised_at, a50, ill, cond = r2.screen(reference_answer, e['uns_g'][:, sel], e['uns_ee'], e['uns_i0'],
                                                   e['uns_mus'], int(e['uns_n_iters']))
     assert np.array_equal(raised, e['uns_raised'][sel]) and np.array_equal(ill, e['uns_ill'][sel])
     assert np.array_equal(raised_at, e['uns_raised_at'][sel])

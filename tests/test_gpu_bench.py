@@ -10,16 +10,19 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# --full: these tests check what the line reports beside the headline (rooflines, modes, the assembly's modes); the plain run
+# itself: test_plain_run_reports_the_headline_and_dumps_the_last_step
 SMALL = ['--n', '64', '--views', '48', '--channels', '96', '--iters', '10', '--steps', '1', '--warmup', '1',
-         '--no-cpu-baseline', '--skip-single-row', '--skip-gn-full-loop']
+         '--no-cpu-baseline', '--skip-single-row', '--skip-gn-full-loop', '--full']
+PLAIN = ['--n', '64', '--views', '48', '--channels', '96', '--iters', '10']
 
 
-def run_bench(*extra, env=None):
+def run_bench(*extra, env=None, base=SMALL):
     e = dict(os.environ)
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         e.pop(k, None)
     e.update(env or {})
-    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *SMALL, *extra], capture_output=True, text=True,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), *base, *extra], capture_output=True, text=True,
                        timeout=900, env=e)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
@@ -52,6 +55,35 @@ def test_plain_command_single_gpu(hip):
     for case in e2e.values():
         assert case['cold']['ok'] and case['cold_no_disk_cache']['ok'] and case['warm']['ok'] and case['warm']['total_s'] > 0
         assert case['bytes']['d2h_per_get_sino'] == 8 * case['rays']
+
+
+def test_plain_run_reports_the_headline_and_dumps_the_last_step(hip, tmp_path):
+    """`bench.py --steps K --warmup W` without --full: exactly K timed steps, the headline keys and nothing measured beside them;
+    --dump-outputs writes the last timed step's results (whole scan at this size, float32 / float64, within 64 MiB), the same
+    arrays from run to run."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f'run{k}'
+        out, _ = run_bench('--steps', '3', '--warmup', '1', '--dump-outputs', str(d), base=PLAIN)
+        assert out['steps'] == 3 and out['warmup'] == 1 and out['full'] is False and out['n_gpus'] == 1
+        assert out['metric'] == 'Siddon ray-energy integrals/sec' and out['unit'] == 'ray-energy integrals/s'
+        assert out['higher_is_better'] is True and out['dtype'] == 'f64' and out['ms_per_step'] > 0
+        assert out['value'] > 0 and out['kernel_ms']['siddon_project'] > 0 and out['kernel_ms']['gn_decompose'] > 0
+        for key in ('roofline', 'roofline_siddon', 'gn_exact', 'noisy_step', 'siddon_reduced_quadrature', 'dropin_e2e', 'cpu_baseline',
+                    'multi_gpu'):
+            assert key not in out, key
+        files = sorted(os.listdir(d))
+        assert files == ['basismat1.npy', 'basismat2.npy', 'sino_log.npy', 'sino_raw.npy']
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs['sino_raw'].shape == arrs['sino_log'].shape == (2, 48, 64, 96) and arrs['sino_raw'].dtype == np.float32
+        assert arrs['basismat1'].shape == (48, 64, 96) and arrs['basismat1'].dtype == np.float64
+        assert out['dumped_outputs'] == {k: list(v.shape) for k, v in arrs.items()}
+        assert np.isfinite(arrs['sino_raw']).all() and (arrs['sino_raw'] > 0).any() and (arrs['basismat1'] != 0).any()
+        dumps.append(arrs)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
 
 
 @pytest.mark.parametrize('scaling,gather', [('strong', None), ('weak', 'direct'), ('strong', 'all'), ('strong', 'root')])

@@ -503,6 +503,38 @@ def test_gather_auto_picks_the_fastest_step_and_prefers_the_north_stars_gather_o
     assert pick_mode({'root': 13.0, 'direct': 12.5, 'all': 12.0}) == 'all'
 
 
+def test_dump_outputs_samples_a_large_scan_at_fixed_rays(tmp_path):
+    """bench/dump.py on a scan whose outputs exceed 64 MiB: the same seeded rays in every array and every run, float32 /
+    float64 only, within the limit, each value the one at its [view][row][channel] index."""
+    import sys
+    import types
+    import torch
+    sys.path.insert(0, ROOT)
+    from bench import dump
+    nV, rows, ch = 40, 256, 256                                           # 2.6e6 rays: 84 MB of outputs
+    g = torch.Generator().manual_seed(7)
+    wl = types.SimpleNamespace(counts=torch.rand((2, nV, rows, ch), generator=g), log_ref=torch.rand((2, nV, rows, ch), generator=g),
+                               a_out=torch.rand((nV, rows, ch, 2), generator=g, dtype=torch.float64), dev=torch.device('cpu'))
+    runs = []
+    for k in range(2):
+        d = tmp_path / f'run{k}'
+        shapes = dump.write(wl, str(d))
+        arrs = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert sorted(arrs) == ['basismat1', 'basismat2', 'sample_index', 'sino_log', 'sino_raw']
+        assert shapes == {k: list(v.shape) for k, v in arrs.items()}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 << 20
+        runs.append(arrs)
+    idx = runs[0]['sample_index'].astype(np.int64)
+    assert idx.size == dump.SAMPLE_RAYS and np.all(np.diff(idx) > 0) and idx[-1] < nV * rows * ch
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+    v, r, c = np.unravel_index(idx, (nV, rows, ch))
+    assert np.array_equal(runs[0]['sino_raw'], wl.counts.numpy()[:, v, r, c])
+    assert np.array_equal(runs[0]['sino_log'], wl.log_ref.numpy()[:, v, r, c])
+    assert np.array_equal(runs[0]['basismat2'], wl.a_out.numpy()[v, r, c, 1])
+
+
 def test_the_committed_bench_line_keeps_the_contract():
     """profiles/r06_final_bench.json (the plain `python bench.py` line of the final tree, cited by README.md / DESIGN.md): every key
     of the bench contract, the metric and unit BASELINE.json names, `roofline` (issued flops / peak, with the survey-unit figure and

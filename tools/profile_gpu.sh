@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 # CPU baseline, the public-boundary timing and the extra Newton launches
 # (--skip-noisy: the noisy step runs the traversal kernel with other outputs - path lengths for the per-bin Poisson sampler - and
 # would be averaged into the step kernel's counters; its own passes: tools/profile_config4.sh <tag> noisy=1 ...)
-LEAN="--steps 1 --warmup 0 --no-cpu-baseline --skip-gn-full-loop --skip-dropin --skip-quadrature --skip-noisy"
+LEAN="--steps 1 --warmup 0 --full --no-cpu-baseline --skip-gn-full-loop --skip-dropin --skip-quadrature --skip-noisy"
 run() {  # name, rocprofv3 args...
   local name=$1; shift
   rocprofv3 "$@" --kernel-trace --output-format csv -d $OUT/$name -- python3 $REPO/bench.py $BENCH_ARGS > $OUT/bench_$name.json 2> $OUT/bench_$name.err
@@ -21,7 +21,7 @@ run() {  # name, rocprofv3 args...
   echo "$name rc=$rc"
   if [ $rc -ne 0 ]; then tail -5 $OUT/bench_$name.err; exit $rc; fi
 }
-BENCH_ARGS="$* --skip-gn-full-loop --skip-dropin --skip-quadrature"
+BENCH_ARGS="$* --full --skip-gn-full-loop --skip-dropin --skip-quadrature"
 run stats --stats
 BENCH_ARGS="$* $LEAN"
 run pmc_fetch --pmc FETCH_SIZE
