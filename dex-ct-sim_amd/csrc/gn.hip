@@ -849,7 +849,7 @@ __device__ __forceinline__ bool gn_exit_or_advance(double n0, double n1, int n_i
 // outside the grid, another fixed point, NaN) is solved the reference's way.
 // Layout: [0],[1] unattenuated signals; [2] 1 / log_range; [3] cells per axis n; [4] ln of the smallest u0 of the grid;
 // [5] cells per unit of ln u0; [6] smallest ratio u1 / u0 of the grid; [7] cells per unit of the ratio; [8],[9] ln of [0],[1];
-// [10] 2 if the tables of the one-step acceptance follow the cells (below), else 0; [11] reserved; then the corners' fixed points
+// [10] 2 if the tables of the one-step acceptance follow the cells (below), else 0; [11] where the power form starts (0: none); then the corners' fixed points
 // as pairs (a0, a1)[(n+1)^2] (row = index along ln u0), then per cell the pair (need, radius)[n^2], then - [10] = 2 - per cell the
 // pair (kappa, eps)[n^2]; the array is 16-byte aligned (pairs are read with one load).
 //
@@ -925,9 +925,54 @@ __device__ __forceinline__ bool gn_start(const double* __restrict__ start, const
   // - close enough for ONE step to land at rounding level with a proven bound, and it costs 36 loads and 100 - 250 FMAs against a
   // step's 2 500.
   const double wx = fx - (double)i, wy = fy - (double)j;
-  auto weights = [](double t_, double (&w)[6], double (&dw)[6]) {
-    // nodes -2 .. 3: w_a = prod_(b != a) (t - x_b) / (x_a - x_b), by prefix and suffix products of p_b = t - x_b; DERIV: and
-    // dw_a / dt by the product rule on the same recurrences (l_(a+1) = l_a p_a: l'_(a+1) = l'_a p_a + l_a)
+  radius = cell.y;
+  if (DERIV) {
+    if (!(start[11] > 0.0)) {            // a start array without the power form (not made by _device_tables): the gate closes
+      s0 = s1 = 0.0;
+      *cell_out = GnCell{i * n + j, t, {0.0, 0.0}, {0.0, 0.0}};
+      return false;
+    }
+    // THE POWER FORM (round 7): the same sextic, per cell as sum_ab C_ab wx^a wy^b (matdecomp._device_tables builds C from
+    // the corners' fixed points on the device, appended to the start array at offset start[11]).  Horner along wy with the
+    // derivative carried along, then along wx: 136 FMAs and no weights, against the Lagrange form's 180 FMAs and ~90
+    // instructions of weights.  It is the same polynomial: s and B agree with the Lagrange form to rounding
+    // (tests/test_gn_power_form.py).
+    const d2* __restrict__ coef = reinterpret_cast<const d2*>(start + (int)start[11]) + (size_t)(i * n + j) * 36;
+    // one row a: p = sum_b C_ab wy^b and d = its derivative along wy, by Horner (the first step of each peeled)
+    auto row = [&](int a, d2& p, d2& d) {
+      const d2* __restrict__ r = coef + 6 * a;
+      p = r[5];
+      d = p;
+      const d2 c4 = r[4];
+      p.x = fma(p.x, wy, c4.x); p.y = fma(p.y, wy, c4.y);
+#pragma unroll
+      for (int b = 3; b >= 0; --b) {
+        const d2 c = r[b];
+        d.x = fma(d.x, wy, p.x); d.y = fma(d.y, wy, p.y);
+        p.x = fma(p.x, wy, c.x); p.y = fma(p.y, wy, c.y);
+      }
+    };
+    d2 v, vx, vy, p, d;                                             // s, d s / d wx, d s / d wy
+    row(5, v, vy);
+    row(4, p, d);
+    vx = v;
+    v.x = fma(v.x, wx, p.x);   v.y = fma(v.y, wx, p.y);
+    vy.x = fma(vy.x, wx, d.x); vy.y = fma(vy.y, wx, d.y);
+#pragma unroll 1
+    for (int a = 3; a >= 0; --a) {
+      row(a, p, d);
+      vx.x = fma(vx.x, wx, v.x); vx.y = fma(vx.y, wx, v.y);
+      v.x = fma(v.x, wx, p.x);   v.y = fma(v.y, wx, p.y);
+      vy.x = fma(vy.x, wx, d.x); vy.y = fma(vy.y, wx, d.y);
+    }
+    s0 = v.x;
+    s1 = v.y;
+    const double kx = -(start[5] * start[2]) * ru0, kt = -(start[7] * start[2]) * ru0;
+    *cell_out = GnCell{i * n + j, t, {vx.x * kx, vx.y * kx}, {vy.x * kt, vy.y * kt}};
+    return ok;
+  }
+  auto weights = [](double t_, double (&w)[6]) {
+    // nodes -2 .. 3: w_a = prod_(b != a) (t - x_b) / (x_a - x_b), by prefix and suffix products of p_b = t - x_b
     const double p0 = t_ + 2.0, p1 = t_ + 1.0, p2 = t_, p3 = t_ - 1.0, p4 = t_ - 2.0, p5 = t_ - 3.0;
     const double l1 = p0, l2 = l1 * p1, l3 = l2 * p2, l4 = l3 * p3, l5 = l4 * p4;          // prod_(b < a) p_b
     const double r4 = p5, r3 = r4 * p4, r2 = r3 * p3, r1 = r2 * p2, r0 = r1 * p1;          // prod_(b > a) p_b
@@ -937,53 +982,26 @@ __device__ __forceinline__ bool gn_start(const double* __restrict__ start, const
     w[3] = l3 * r3 * (1.0 / 12.0);
     w[4] = l4 * r4 * (-1.0 / 24.0);
     w[5] = l5 * (1.0 / 120.0);
-    if (DERIV) {
-      const double dl1 = 1.0, dl2 = fma(dl1, p1, l1), dl3 = fma(dl2, p2, l2), dl4 = fma(dl3, p3, l3), dl5 = fma(dl4, p4, l4);
-      const double dr4 = 1.0, dr3 = fma(dr4, p4, r4), dr2 = fma(dr3, p3, r3), dr1 = fma(dr2, p2, r2), dr0 = fma(dr1, p1, r1);
-      dw[0] = dr0 * (-1.0 / 120.0);
-      dw[1] = fma(dl1, r1, l1 * dr1) * (1.0 / 24.0);
-      dw[2] = fma(dl2, r2, l2 * dr2) * (-1.0 / 12.0);
-      dw[3] = fma(dl3, r3, l3 * dr3) * (1.0 / 12.0);
-      dw[4] = fma(dl4, r4, l4 * dr4) * (-1.0 / 24.0);
-      dw[5] = dl5 * (1.0 / 120.0);
-    }
   };
-  double cx[6], cy[6], dx[6], dy[6];
-  weights(wx, cx, dx);
-  weights(wy, cy, dy);
+  double cx[6], cy[6];
+  weights(wx, cx);
+  weights(wy, cy);
   const int i0c = i > 2 ? i - 2 : 0, j0c = j > 2 ? j - 2 : 0;               // (closed border cells never get here with ok)
   const int base = (i0c <= n - 5 ? i0c : n - 5) * (n + 1) + (j0c <= n - 5 ? j0c : n - 5);
   s0 = 0.0;
   s1 = 0.0;
-  double ax0 = 0.0, ax1 = 0.0, at0 = 0.0, at1 = 0.0;                         // DERIV: d s / d fx, d s / d fy (cell units)
-  // (rows per trip: 2 - twelve loads in flight, not thirty-six: registers at the kernel's tightest spot; 1 with the derivatives,
-  // whose four more row sums and twelve more weights spilled 8 registers at 2)
-#pragma unroll DERIV ? 1 : DEXCT_GN_INTERP_UNROLL
+  // (rows per trip: 2 - twelve loads in flight, not thirty-six: registers at the kernel's tightest spot)
+#pragma unroll DEXCT_GN_INTERP_UNROLL
   for (int p = 0; p < 6; ++p) {
-    double ra = 0.0, rb = 0.0, da = 0.0, db = 0.0;
+    double ra = 0.0, rb = 0.0;
 #pragma unroll
     for (int q = 0; q < 6; ++q) {
       const d2 r = roots[base + p * (n + 1) + q];
       ra = fma(cy[q], r.x, ra);
       rb = fma(cy[q], r.y, rb);
-      if (DERIV) {
-        da = fma(dy[q], r.x, da);
-        db = fma(dy[q], r.y, db);
-      }
     }
     s0 = fma(cx[p], ra, s0);
     s1 = fma(cx[p], rb, s1);
-    if (DERIV) {
-      ax0 = fma(dx[p], ra, ax0);
-      ax1 = fma(dx[p], rb, ax1);
-      at0 = fma(cx[p], da, at0);
-      at1 = fma(cx[p], db, at1);
-    }
-  }
-  radius = cell.y;
-  if (DERIV) {
-    const double kx = -(start[5] * start[2]) * ru0, kt = -(start[7] * start[2]) * ru0;     // cells per unit x (t) x d x (t) / d ln g
-    *cell_out = GnCell{i * n + j, t, {ax0 * kx, ax1 * kx}, {at0 * kt, at1 * kt}};
   }
   return ok;
 }

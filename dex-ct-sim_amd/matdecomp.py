@@ -291,6 +291,41 @@ def _gate_to_disk(path, start_h, stats):
         pass                              # (a read-only home directory: the table is simply not kept)
 
 
+def _lagrange_to_power():
+    """M[p, a]: the coefficient of w^a in the Lagrange basis polynomial of node p of the nodes -2 .. 3 (csrc/gn.hip, gn_start)."""
+    nodes = np.arange(-2.0, 4.0)
+    m = np.zeros((6, 6))
+    for p in range(6):
+        c = np.array([1.0])
+        for b in range(6):
+            if b != p:
+                c = np.convolve(c, np.array([-nodes[b], 1.0])) / (nodes[p] - nodes[b])
+        m[p] = c
+    return m
+
+
+def power_form(start):
+    """The start array of the short cut with the power form of its interpolant appended (csrc/gn.hip, gn_start<DERIV>): per
+    cell (i, j) the 6 x 6 coefficients C_ab (pairs (a0, a1)) of the same sextic the Lagrange form evaluates on the corners'
+    fixed points of rows clamp(i - 2, 0, n - 5) + 0..5 and columns clamp(j - 2, 0, n - 5) + 0..5, as sum_ab C_ab wx^a wy^b in
+    the cell's own coordinates; word [11] of the header is set to the offset (in doubles, even: 16-byte pairs) where they
+    start.  Works on any device (float64 throughout); the header and tables before the appended part are not changed."""
+    from . import quadrature
+    start = start.to(torch.float64)
+    n = int(start[3].item())
+    roots = start[quadrature.START_HEADER:quadrature.START_HEADER + 2 * (n + 1) ** 2].view(n + 1, n + 1, 2)
+    win = roots.unfold(0, 6, 1).unfold(1, 6, 1)                                  # [u, v, k, p, q]: the window at (u, v)
+    b = torch.clamp(torch.arange(n, device=start.device) - 2, 0, n - 5)
+    m = torch.as_tensor(_lagrange_to_power(), dtype=torch.float64, device=start.device)
+    coef = torch.einsum('ijkpq,pa,qb->ijabk', win[b][:, b], m, m).contiguous()
+    off = start.numel() + (start.numel() & 1)
+    out = torch.zeros(off + coef.numel(), dtype=torch.float64, device=start.device)
+    out[:start.numel()] = start
+    out[11] = float(off)
+    out[off:] = coef.reshape(-1)
+    return out
+
+
 def _device_tables(i0, mus, dev, want_gate, cal_tol=1.0e-12):
     """(i0_d [2, nBins, nE], mus_d [2, nE], gate) for host or device tables, cached by content; ``want_gate``: prepare the short
     cut - gate = {'start': device array | None, 'ill_posed': bool, 'stats': ...} (None when not wanted); ``cal_tol``: the
@@ -328,7 +363,7 @@ def _device_tables(i0, mus, dev, want_gate, cal_tol=1.0e-12):
             gate['stats'] = stats
             gate['ill_posed'] = bool(quadrature.pair_is_ill_posed(stats))
             if start_h is not None and not gate['ill_posed'] and stats.get('open_share', 0.0) >= 0.1:
-                gate['start'] = to_dev(start_h, torch.float64, dev)
+                gate['start'] = power_form(to_dev(start_h, torch.float64, dev))
         ent[('gate', cal_tol)] = gate
     return ent['i0'], ent['mus'], (ent.get(('gate', cal_tol)) if want_gate else None)
 
