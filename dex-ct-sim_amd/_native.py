@@ -15,7 +15,7 @@ SYMBOLS = ['dexct_strerror', 'dexct_abi_version', 'dexct_last_hip_error', 'dexct
            'dexct_cone_layout', 'dexct_cone_project_rows', 'dexct_volume_pack2', 'dexct_siddon_project_packed', 'dexct_volume_groups_pack2',
            'dexct_siddon_project_grouped_packed', 'dexct_poisson_detect', 'dexct_vmi', 'dexct_label_moments', 'dexct_fdk_backproject', 'dexct_sino_allgather', 'dexct_sino_gather', 'dexct_transpose_log', 'dexct_host_pin', 'dexct_host_touch', 'dexct_host_unpin', 'dexct_download',
            'dexct_volume_ids', 'dexct_volume_remap', 'dexct_fbp_parker', 'dexct_sino_log', 'dexct_cone_layout_groups', 'dexct_cone_project_grouped',
-           'dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes']
+           'dexct_bhc_linearize', 'dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes']
 
 
 class FanGeom(C.Structure):
@@ -113,6 +113,7 @@ def load():
     lib.dexct_add_noise.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, C.c_uint64, vp]
     lib.dexct_volume_groups.argtypes = [vp, i64, i32, vp, vp]
     lib.dexct_vmi.argtypes = [vp, vp, i64, f64, f64, f64, i32, vp, vp]
+    lib.dexct_bhc_linearize.argtypes = [vp, i64, vp, i32, i32, i32, i32, vp, vp]
     lib.dexct_label_moments.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     lib.dexct_sino_allgather.argtypes = [vp, vp, i64, vp, vp]
     lib.dexct_sino_gather.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i64), i32, i32, i32, vp, vp]

@@ -84,15 +84,20 @@ def default_slices(ct):
     return ct.N_rows, -0.5 * (ct.N_rows - 1) * ct.h_iso, ct.h_iso
 
 
-def recon_device(sino_d, ct, N_matrix, FOV, ramp, window=None, slices=None):
+def recon_device(sino_d, ct, N_matrix, FOV, ramp, window=None, slices=None, bhc=None):
     """sino_d: device float32 [N_proj, N_channels] or [N_proj, N_rows, N_channels] -> image tensor
     [N_matrix, N_matrix] or [N_rows, N_matrix, N_matrix] (float32, 1/cm).  A cone-beam scanner (``ct.cone``) is
-    reconstructed with Feldkamp's algorithm onto ``slices = (n_slices, z_first [cm], dz [cm])``."""
+    reconstructed with Feldkamp's algorithm onto ``slices = (n_slices, z_first [cm], dz [cm])``.  ``bhc``: a
+    ``bhc.LinearizationTable`` - the sinogram is linearised first (into a new buffer; sino_d is left as it is), before
+    Parker's weights, which a nonlinear map must not follow."""
     lib = _native.load()
     dev = sino_d.device
     three_d = sino_d.dim() == 3
     s = sino_d if three_d else sino_d[:, None, :]
     s = s.contiguous()
+    if bhc is not None:
+        from .bhc import linearize_device
+        s = linearize_device(s, bhc)
     n_views, n_rows, n_ch = s.shape
     if n_views != ct.N_proj or n_ch != ct.N_channels:
         raise ValueError(f'sinogram {tuple(sino_d.shape)} does not match the scanner ({ct.N_proj} x {ct.N_channels})')
@@ -135,11 +140,14 @@ def recon_device(sino_d, ct, N_matrix, FOV, ramp, window=None, slices=None):
     return img if three_d else img[0]
 
 
-def get_recon(sino, ct, spec, N_matrix, FOV, ramp, window=None, slices=None):
+def get_recon(sino, ct, spec, N_matrix, FOV, ramp, window=None, slices=None, bhc=None):
     """Drop-in for ``recon_raw, recon_HU = get_recon(sino, ct, spec, N_matrix, FOV, ramp)`` (main.py:134).
     ``window``: apodisation of the ramp (WINDOWS; default ``DEXCT_FBP_WINDOW`` or the plain band-limited ramp).
     Cone-beam sinograms ([N_proj, N_rows, N_channels] of a ``cone=True`` scanner) are reconstructed with Feldkamp's
-    algorithm into ``slices = (n_slices, z_first, dz)`` (default: default_slices)."""
+    algorithm into ``slices = (n_slices, z_first, dz)`` (default: default_slices).
+    ``bhc``: beam-hardening correction of the log sinogram before the reconstruction (bhc.py) - a material ('water',
+    'bone', a Material or (formula, density)) linearised for ``spec`` and the scanner's detector, or a prebuilt
+    ``bhc.LinearizationTable``.  recon_HU stays 1000 (raw - water_mu) / water_mu: water reads 0 HU after water BHC."""
     dev = device()
     sino_d = to_dev(np.asarray(sino, dtype=np.float32), torch.float32, dev)
     bad = int((~torch.isfinite(sino_d)).sum().item())
@@ -149,6 +157,10 @@ def get_recon(sino, ct, spec, N_matrix, FOV, ramp, window=None, slices=None):
         import warnings
         warnings.warn(f'get_recon: {bad} non-finite sinogram value(s) set to 0 before filtering', RuntimeWarning)
         sino_d = torch.nan_to_num(sino_d, nan=0.0, posinf=0.0, neginf=0.0)
+    if bhc is not None:
+        from . import bhc as bhc_mod
+        table = bhc if isinstance(bhc, bhc_mod.LinearizationTable) else bhc_mod.linearization_table(ct, spec, bhc)
+        bhc_mod.linearize_device(sino_d, table, out=sino_d)         # sino_d is this call's own copy
     raw = recon_device(sino_d, ct, N_matrix, FOV, ramp, window, slices).cpu().numpy()
     mu_w = water_mu(ct, spec)
     return raw, (1000.0 * (raw - mu_w) / mu_w).astype(np.float32)

@@ -7,7 +7,9 @@ for every run in the parameter file, for every dual-energy spectrum pair:
   2. decompose the two raw sinograms into basis-material sinograms with 50 Newton iterations
      (:153) and write ``matdecomp_<s1>_<s2>_<d1>uGy_<d2>uGy/mat{1,2}_sino_float32.bin`` (:154-155).
   3. when ``back_project`` is set: reconstruct every log sinogram (:134 -> recon_raw/recon_HU .bin, :135-136)
-     and both basis-material sinograms (:168 -> mat{1,2}_recon_float32.bin, :169).
+     and both basis-material sinograms (:168 -> mat{1,2}_recon_float32.bin, :169); with ``--bhc water bone`` also the
+     beam-hardening-corrected images of every log sinogram, ``recon_{water,bone}BHC_{raw,HU}_float32.bin`` (the files
+     the reference's plots.py:184-195 reads; basis-material sinograms are linear in thickness already and get none).
 
 Differences from the reference script, all on purpose: inputs are command-line options instead of
 edited source lines (:80-82, :101-103); figures are off unless --show; both spectra of a pair are
@@ -79,6 +81,9 @@ def main(argv=None):
     ap.add_argument('--seed', type=int, default=0, help='seed of the counter-based noise generator')
     ap.add_argument('--window', default=None, choices=['rect', 'sinc', 'cosine', 'hann', 'hamming'],
                     help='apodisation of the reconstruction ramp (default: DEXCT_FBP_WINDOW or rect)')
+    ap.add_argument('--bhc', nargs='*', default=[], choices=['water', 'bone'],
+                    help='also write beam-hardening-corrected reconstructions of every log sinogram, linearised for '
+                         'these reference materials (recon_<m>BHC_{raw,HU}_float32.bin beside recon_raw)')
     args = ap.parse_args(argv)
 
     import torch.distributed as dist
@@ -122,6 +127,10 @@ def main(argv=None):
                         recon_raw, recon_HU = get_recon(sino_log, ct, spec, N_matrix, FOV, ramp, window=args.window)
                         recon_raw.astype(np.float32).tofile(sub_dir + 'recon_raw_float32.bin')
                         recon_HU.astype(np.float32).tofile(sub_dir + 'recon_HU_float32.bin')
+                        for m in dict.fromkeys(args.bhc):
+                            bhc_raw, bhc_HU = get_recon(sino_log, ct, spec, N_matrix, FOV, ramp, window=args.window, bhc=m)
+                            bhc_raw.astype(np.float32).tofile(sub_dir + f'recon_{m}BHC_raw_float32.bin')
+                            bhc_HU.astype(np.float32).tofile(sub_dir + f'recon_{m}BHC_HU_float32.bin')
                         if args.show:
                             show('Raw reconstruction [1/cm]', recon_raw, 'Hounsfield Units', recon_HU)
             sub_dir = os.path.join(out_dir, f'matdecomp_{s1}_{s2}_{int(d1 * 1000):04}uGy_{int(d2 * 1000):04}uGy/')

@@ -9,7 +9,7 @@ plots.py:276-312) can be run on the engine's outputs:
   measure_roi(M, roi_info, give_roi, ax)         plots.py:146-158   (HIP: dexct_label_moments)
   crop_img(M, crop)                              plots.py:167-170
   get_xcat_mask(M, threshold)                    plots.py:226-231
-  get_img_ct / get_img_basismats                 plots.py:173-207   (paths of main.py's output tree)
+  get_img_ct / get_img_ct_BHC / get_img_basismats   plots.py:173-207   (paths of main.py's output tree)
 
 and two sweeps the reference writes as Python loops over energies (one make_vmi + one measurement per energy):
 
@@ -95,6 +95,19 @@ def get_img_ct(phantom_id, spec_id, dose, crop=None, units='HU', N_matrix=512, o
     assert units in ('HU', 'raw')
     path = os.path.join(out_dir, f'{run_prefix}{phantom_id}', f'{spec_id}_{int(dose * 1000):04}uGy',
                         f'recon_{units}_float32.bin')
+    M = np.fromfile(path, dtype=np.float32).reshape([N_matrix, N_matrix])
+    return M if crop is None else crop_img(M, crop)
+
+
+def get_img_ct_BHC(phantom_id, spec_id, dose, crop=None, units='HU', N_matrix=512, out_dir='output', run_prefix='mvkv_',
+                   bhc='bone'):
+    """Beam-hardening-corrected reconstruction written by ``main.py --bhc`` (plots.py:184-195): the file name of the
+    reference, in the same directory as get_img_ct's image (the reference reads a separate run, mvkv_r2/{phantom}_bhc_{spec}/,
+    which none of its shipped steps writes)."""
+    assert units in ('HU', 'raw')
+    assert bhc in ('bone', 'water')
+    path = os.path.join(out_dir, f'{run_prefix}{phantom_id}', f'{spec_id}_{int(dose * 1000):04}uGy',
+                        f'recon_{bhc}BHC_{units}_float32.bin')
     M = np.fromfile(path, dtype=np.float32).reshape([N_matrix, N_matrix])
     return M if crop is None else crop_img(M, crop)
 
