@@ -174,25 +174,30 @@ def _host_tables(x):
     return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64)
 
 
-def _walk(lib, dev, i0_d, mus_d, n_e, g, cal_tol):
+def _walk(lib, dev, i0_d, mus_d, n_e, g, cal_tol, alloc=None):
     """The reference's iteration (the library's own kernel, full tables, from 1e-6, counting steps) on counts g [n, 2]:
-    (steps until the tolerance rule fired | 255, where it ended)."""
-    g_d = to_dev(np.ascontiguousarray(g.T), torch.float64, dev)
-    n_c = g_d.shape[1]
-    a_c = torch.empty((n_c, 2), dtype=torch.float64, device=dev)
-    k_c = torch.empty(n_c, dtype=torch.uint8, device=dev)
-    ws = torch.empty(lib.dexct_gn_workspace_bytes(n_e, 1), dtype=torch.uint8, device=dev)
+    (steps until the tolerance rule fired | 255, where it ended).  ``alloc(name, shape, dtype)``: where the launch's buffers
+    come from (default torch.empty on ``dev``; tests/test_gpu_bounds.py passes guarded ones)."""
+    if alloc is None:
+        alloc = lambda name, shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+    n_c = g.shape[0]
+    g_d = alloc('g', (2, n_c), torch.float64)
+    g_d.copy_(torch.from_numpy(np.ascontiguousarray(g.T, dtype=np.float64)))
+    a_c = alloc('a', (n_c, 2), torch.float64)
+    k_c = alloc('iterations', (n_c,), torch.uint8)
+    ws = alloc('workspace', (lib.dexct_gn_workspace_bytes(n_e, 1),), torch.uint8)
     _native.check(lib.dexct_gn_decompose(ptr(g_d[0]), ptr(g_d[1]), 1, n_c, ptr(i0_d), ptr(mus_d), n_e, 1, 1, 254, 0, 0, None, 0.95,
                                          ptr(a_c), _native.gn_options(cal_tol, 0, 0, 1, _native.GN_PASS_COUNT, k_c.data_ptr()),
                                          ptr(ws), stream_ptr()), 'dexct_gn_decompose (gate calibration)')
     return k_c.cpu().numpy(), a_c.cpu().numpy()
 
 
-def calibrate_gate(i0_h, mus_h, i0_d, mus_d, dev, cal_tol):
+def calibrate_gate(i0_h, mus_h, i0_d, mus_d, dev, cal_tol, alloc=None):
     """THE GATE of the short cut (csrc/gn.hip, gn_start): the reference's iteration run on the counts at the corners of a cell
     grid in data space; where it ends, after how many steps, and how smoothly that varies decides where pixels may take the
     short cut and where they start; then the table is checked against what it stands for at every cell's centre.
-    Returns (start array or None, stats) - stats says what the calibration saw of the pair (quadrature.pair_is_ill_posed)."""
+    Returns (start array or None, stats) - stats says what the calibration saw of the pair (quadrature.pair_is_ill_posed).
+    ``alloc``: see _walk."""
     from . import quadrature
     i0_2 = i0_h.reshape(2, -1)
     pieces = quadrature.newton_start_grid(i0_2, mus_h)
@@ -201,9 +206,9 @@ def calibrate_gate(i0_h, mus_h, i0_d, mus_d, dev, cal_tol):
     pieces['device'] = dev                    # (the energy sums of the table assembly run there: quadrature._model_sums)
     lib = _native.load()
     n_e = i0_2.shape[1]
-    steps, roots = _walk(lib, dev, i0_d, mus_d, n_e, pieces['corner_g'], cal_tol)
+    steps, roots = _walk(lib, dev, i0_d, mus_d, n_e, pieces['corner_g'], cal_tol, alloc)
     start_h, share, stats = quadrature.assemble_start(pieces, steps, roots)
-    start_h, share, n_bad = quadrature.validate_start(start_h, pieces, *_walk(lib, dev, i0_d, mus_d, n_e, quadrature.cell_centres(pieces), cal_tol))
+    start_h, share, n_bad = quadrature.validate_start(start_h, pieces, *_walk(lib, dev, i0_d, mus_d, n_e, quadrature.cell_centres(pieces), cal_tol, alloc))
     stats = dict(stats, grid=True, open_share=float(share), centres_failed=int(n_bad))
     return start_h, stats
 
