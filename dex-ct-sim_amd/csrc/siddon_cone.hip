@@ -1040,22 +1040,7 @@ extern "C" int dexct_cone_project_grouped(const dexct_fan_geom* geom, const dexc
   if (n_materials > DEXCT_MAX_MATERIALS) return DEXCT_ERANGE;
   const int rc = cone_rows_checks(geom, view_begin, view_end, n_energies, n_spectra, max_abs_dz);
   if (rc != DEXCT_OK) return rc;
-  hipStream_t st = as_stream(stream);
-  // ---- one traversal per group of three materials: lengths [cm] into the planes of acc_scratch
-  ConeArgs a;
-  fill_cone_args(a, geom, plan, view_cs, chan_cs, row_z, src_z, view_begin, view_end, n_materials, n_energies, n_spectra, counts,
-                 nullptr, nullptr);
-  set_cone_noise(a, nullptr, nullptr);
-  a.acc_out = acc_scratch;
-  const size_t layout_bytes = (size_t)dexct_cone_layout_bytes(geom->nx, geom->ny, geom->nz);
-  const int n_groups = (n_materials + 2) / 3;
-  for (int g = 0; g < n_groups; ++g) {
-    a.mat_base = 3 * g;
-    const int left = n_materials - 3 * g;
-    const int lrc = launch_cone_rows(a, vol_zcg + (size_t)g * layout_bytes, left >= 3 ? 3 : left, mu, weights, nullptr, st);
-    if (lrc != DEXCT_OK) return lrc;
-  }
-  // ---- one detection pass over all planes (the pass of the stacked fan's material groups, reading lengths)
+  // ---- the arguments of the detection pass first: a refused call (noise / log combination) must have launched nothing
   ProjArgs d;
   d.g = *geom;
   d.plan = plan;
@@ -1074,6 +1059,22 @@ extern "C" int dexct_cone_project_grouped(const dexct_fan_geom* geom, const dexc
   d.acc_lengths = 1;
   { const int nrc = set_noise(d, view_begin, weights2, variance, noise); if (nrc != DEXCT_OK) return nrc; }
   if (set_log_out(d, log_out, d.sample ? nullptr : variance) != DEXCT_OK) return DEXCT_EINVAL;
+  hipStream_t st = as_stream(stream);
+  // ---- one traversal per group of three materials: lengths [cm] into the planes of acc_scratch
+  ConeArgs a;
+  fill_cone_args(a, geom, plan, view_cs, chan_cs, row_z, src_z, view_begin, view_end, n_materials, n_energies, n_spectra, counts,
+                 nullptr, nullptr);
+  set_cone_noise(a, nullptr, nullptr);
+  a.acc_out = acc_scratch;
+  const size_t layout_bytes = (size_t)dexct_cone_layout_bytes(geom->nx, geom->ny, geom->nz);
+  const int n_groups = (n_materials + 2) / 3;
+  for (int g = 0; g < n_groups; ++g) {
+    a.mat_base = 3 * g;
+    const int left = n_materials - 3 * g;
+    const int lrc = launch_cone_rows(a, vol_zcg + (size_t)g * layout_bytes, left >= 3 ? 3 : left, mu, weights, nullptr, st);
+    if (lrc != DEXCT_OK) return lrc;
+  }
+  // ---- one detection pass over all planes (the pass of the stacked fan's material groups, reading lengths)
   const Tables t{mu, weights, weights2};
   return launch_detect_any(d, t, st);
 }

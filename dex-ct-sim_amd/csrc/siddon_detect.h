@@ -60,7 +60,9 @@ inline int set_noise(ProjArgs& a, int32_t view_begin, const float* weights2, con
   if (!weights2) return (variance || sample) ? DEXCT_EINVAL : DEXCT_OK;
   if (!variance && !sample) return DEXCT_EINVAL;
   if (sample) {
-    if (a.n_spectra > 2 || a.n_materials > 48) return DEXCT_ERANGE;      // (the fused variance: two spectrum slots, register lengths)
+    // (the fused variance: two spectrum slots, register lengths; a single material goes to detect_kernel_chunked, which draws
+    // no sample - only dexct_cone_project_grouped admits one material at all)
+    if (a.n_spectra > 2 || a.n_materials > 48 || a.n_materials < 2) return DEXCT_ERANGE;
     a.sample = 1;
     a.seed_lo = (uint32_t)noise->seed;
     a.seed_hi = (uint32_t)(noise->seed >> 32);

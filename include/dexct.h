@@ -171,9 +171,14 @@ int dexct_siddon_project(const dexct_fan_geom* geom, const dexct_ray_plan* plan,
  *   detection pass forms material 0 from the chord and applies the tables; outputs as dexct_siddon_project.
  *   Bit-identical path lengths to the single-pass kernels (per-material sums are independent).
  *   noise (ABI 6, the three group entry points; struct dexct_noise): with weights2 and noise->sample the detection pass sums the
- *   variance with the signal and draws the sample itself (<= 2 spectra, <= 48 materials, else DEXCT_ERANGE: use the variance
+ *   variance with the signal and draws the sample itself (<= 2 spectra, 2..48 materials, else DEXCT_ERANGE: use the variance
  *   output + dexct_add_noise, which draws the same sample); variance is then optional and log_out receives the log of the sampled
- *   counts.  weights2 without a sample needs the variance output (and admits no log_out). */
+ *   counts.  weights2 without a sample needs the variance output (and admits no log_out).  A single material with
+ *   noise->sample (only dexct_cone_project_grouped takes one material at all) is REFUSED with DEXCT_ERANGE: its detection is the
+ *   general kernel of the 49+ materials, which draws no sample.  Every noise / log argument error of the three entry points (and
+ *   every error of a size or pointer argument checked on entry) is returned before the first launch: such a refused call has
+ *   touched no buffer, acc_scratch included.  (A ray count beyond what one detection launch takes, > 2^31 blocks, is still
+ *   found after the group passes were queued.) */
 int dexct_volume_groups(const uint8_t* vol_zf, int64_t n_voxels, int32_t n_materials, uint8_t* codes, void* stream);
 int dexct_siddon_project_grouped(const dexct_fan_geom* geom, const dexct_ray_plan* plan, int32_t view_begin,
                                  int32_t view_end, const uint8_t* codes, int32_t n_materials, int32_t n_energies,
