@@ -267,7 +267,11 @@ int dexct_cone_project_grouped(const dexct_fan_geom* geom, const dexct_ray_plan*
 /* counts = max(counts + sqrt(variance) * z, 1e-20), z ~ N(0, 1) from Philox4x32-10 with counter (view_offset + view, row,
  * channel, 0) and key seed - one block per detector pixel, spectrum s takes the s-th normal of its two Box-Muller pairs (ABI 6;
  * struct dexct_noise: the projection kernels that sample by themselves draw exactly this) - : independent of view sharding and
- * of the layout (0 / 1 as above).  The clip keeps a log sinogram finite. */
+ * of the layout (0 / 1 as above).  The clip keeps a log sinogram finite: every output is finite and >= 1e-20, whatever comes in.
+ * A variance that is zero, negative or NaN counts as zero (the count comes back bit for bit).  A NaN count BECOMES 1e-20 - the
+ * clip is an fmaxf, which returns its other operand for a NaN one - so a NaN does not pass through this call (nor through the
+ * kernels that draw the sample themselves, which share the code): look for it in the noise-free counts.  Intended, and
+ * asserted by tests/test_gpu_noise.py. */
 int dexct_add_noise(float* counts, const float* variance, int32_t n_spectra, int32_t n_views, int32_t n_rows,
                     int32_t n_channels, int32_t layout, int32_t view_offset, uint64_t seed, void* stream);
 
