@@ -853,19 +853,22 @@ __device__ __forceinline__ bool gn_exit_or_advance(double n0, double n1, int n_i
 // as pairs (a0, a1)[(n+1)^2] (row = index along ln u0), then per cell the pair (need, radius)[n^2], then - [10] = 2 - per cell the
 // pair (kappa, eps)[n^2]; the array is 16-byte aligned (pairs are read with one load).
 //
-// ONE STEP INSTEAD OF TWO (DEXCT_GN_FLAG_ONE_STEP).  A step from a start value s at distance e0 of the fixed point a* that
-// provably leaves  e1 <= eps e0 + kappa e0^2  (the chord step above; round 5: a Gauss-Newton step with eps = 0) measures e0 by its
-// own length, d1 = |m - s| >= e0 - e1.  The host tabulates (kappa, eps) per cell - kappa from the second derivatives of the
-// misfit at the tabulated fixed points (2.5 x the largest value at the corners of the cell and of the eight around it), eps
-// from the table's own gradient against the exact Jacobians at the cell's corners and centre (4 x the largest of the cell and the
-// eight around it); infinity where a corner or centre does not count.  A pixel whose step satisfies
+// ONE STEP INSTEAD OF TWO (DEXCT_GN_FLAG_ONE_STEP).  A step from a start value s at distance e0 of the fixed point a* that leaves
+// e1 <= eps e0 + kappa e0^2  (the chord step above; round 5: a Gauss-Newton step with eps = 0) measures e0 by its own length, d1 =
+// |m - s| >= e0 - e1.  Of the two constants kappa is PROVEN (a bound on the second derivatives), eps is MEASURED: sampled at five
+// points of a cell, times a safety factor - nothing proves the derivative of the interpolant worst there.  The witness over the
+// plane is tests/test_gpu_gn_plane.py (every mode against an extended-precision root: cell corners, edges, the thick end, the rim
+// of the physical ratios, the frontier of the open cells).  The host tabulates (kappa, eps) per cell - kappa from the second
+// derivatives of the misfit at the tabulated fixed points (2.5 x the largest value at the corners of the cell and of the eight
+// around it), eps from the table's own gradient against the exact Jacobians at the cell's corners and centre (4 x the largest of
+// the cell and the eight around it); infinity where a corner or centre does not count.  A pixel whose step satisfies
 //     (kappa d1 + eps) d1 <= stop_tol / 4 * max(min(|a0|, |a1|), 1)
-// has what the tolerance rule asks of two steps - a bound on the distance it still has to go, below stop_tol / 4 of its size
-// (here even of its SMALLER component: the one-step results are compared with the exact count per component) -
-// from one, and ends there; every other pixel goes on with full Newton steps and the rule, as before.  With the sextic
-// interpolant d1 is 1e-11 of |a| at the median point of the data plane (5e-10 at the 90th percentile, 1e-8 at the 99th: the thick
-// end at the edges of the physical ratios), kappa |a| is 100 on average, eps 2e-8 at the median point (2e-7 / 1e-5 at the 90th /
-// 99th percentile: it shrinks and grows with d1): ~99 % of the plane passes with orders to spare, the rest takes full Newton steps.
+// has what the tolerance rule asks of two steps - a bound on the distance it still has to go, below stop_tol / 4 of its size (here
+// even of its SMALLER component: the one-step results are compared with the exact count per component) - from one, and ends there;
+// every other pixel goes on with full Newton steps and the rule, as before.  With the sextic interpolant d1 is 1e-11 of |a| at the
+// median point of the data plane (5e-10 at the 90th percentile, 1e-8 at the 99th: the thick end at the edges of the physical
+// ratios), kappa |a| is 100 on average, eps 2e-8 at the median point (2e-7 / 1e-5 at the 90th / 99th percentile: it shrinks and
+// grows with d1): ~99 % of the plane passes with orders to spare, the rest takes full Newton steps.
 constexpr int kStartHeader = 12;
 #ifndef DEXCT_GN_INTERP_UNROLL
 #define DEXCT_GN_INTERP_UNROLL 2      // rows of the 6 x 6 interpolation per loop trip (A/B: tools/probes/build_variant.sh)
@@ -896,7 +899,9 @@ struct GnCell { int idx; double t, Bx[2], Bt[2]; };      // idx: the cell, for i
 // d ln g_k), the first factor from the derivative weights of the Lagrange basis, the second analytic (u_k = (ln air_k - ln g_k) /
 // log_range, x = ln u0, t = u1 / u0:  dx / d ln g0 = -1 / (log_range u0),  dt / d ln g0 = t / (log_range u0),  dt / d ln g1 =
 // -1 / (log_range u0)).  No table of Jacobians, no load; its error shrinks with the interpolant's own (eps ~ e0 / cell x cond):
-// 2e-8 at the median point of the plane, where a float32 table of the inverse stopped at 1e-5 (rounding x cond(L) = 200).
+// 2e-8 at the median point of the plane, where a float32 table of the inverse stopped at 1e-5 (rounding x cond(L) = 200).  That
+// error - eps of the one-step acceptance - is measured by the host at the cells' corners and centres, not bounded
+// (quadrature.validate_start); tests/test_gpu_gn_plane.py checks what it lets through between those points.
 template <bool DERIV = false>
 __device__ __forceinline__ bool gn_start(const double* __restrict__ start, const double* __restrict__ lds_pow, int n_iters,
                                          double g0, double g1, double& s0, double& s1, double& radius, GnCell* cell_out = nullptr) {
@@ -922,8 +927,8 @@ __device__ __forceinline__ bool gn_start(const double* __restrict__ start, const
   // within two of the border of the grid are closed by the host).  The fixed point is an analytic function of (ln u0, u1 / u0);
   // at 256 cells per axis the sextic interpolant is within 1e-11 of |a| of the pixel's own fixed point at the median point of the
   // plane, 5e-10 at the 90th percentile (the Catmull-Rom interpolant of round 4, third order: 2e-6; tools/probes/gn_interp_cpu.py)
-  // - close enough for ONE step to land at rounding level with a proven bound, and it costs 36 loads and 100 - 250 FMAs against a
-  // step's 2 500.
+  // - close enough for ONE step to land at rounding level with a bound (kappa proven, eps measured: see ONE STEP above), and it
+  // costs 36 loads and 100 - 250 FMAs against a step's 2 500.
   const double wx = fx - (double)i, wy = fy - (double)j;
   radius = cell.y;
   if (DERIV) {
