@@ -15,7 +15,8 @@ SYMBOLS = ['dexct_strerror', 'dexct_abi_version', 'dexct_last_hip_error', 'dexct
            'dexct_cone_layout', 'dexct_cone_project_rows', 'dexct_volume_pack2', 'dexct_siddon_project_packed', 'dexct_volume_groups_pack2',
            'dexct_siddon_project_grouped_packed', 'dexct_poisson_detect', 'dexct_vmi', 'dexct_label_moments', 'dexct_fdk_backproject', 'dexct_sino_allgather', 'dexct_sino_gather', 'dexct_transpose_log', 'dexct_host_pin', 'dexct_host_touch', 'dexct_host_unpin', 'dexct_download',
            'dexct_volume_ids', 'dexct_volume_remap', 'dexct_fbp_parker', 'dexct_sino_log', 'dexct_cone_layout_groups', 'dexct_cone_project_grouped',
-           'dexct_bhc_linearize', 'dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes']
+           'dexct_bhc_linearize', 'dexct_image_project', 'dexct_image_backproject', 'dexct_sirt_residual', 'dexct_sirt_update',
+           'dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes']
 
 
 class FanGeom(C.Structure):
@@ -114,6 +115,10 @@ def load():
     lib.dexct_volume_groups.argtypes = [vp, i64, i32, vp, vp]
     lib.dexct_vmi.argtypes = [vp, vp, i64, f64, f64, f64, i32, vp, vp]
     lib.dexct_bhc_linearize.argtypes = [vp, i64, vp, i32, i32, i32, i32, vp, vp]
+    lib.dexct_image_project.argtypes = [C.POINTER(FanGeom), vp, i32, i32, i32, vp, vp, vp, vp]
+    lib.dexct_image_backproject.argtypes = [C.POINTER(FanGeom), vp, i32, i32, i32, vp, vp, vp, i32, vp]
+    lib.dexct_sirt_residual.argtypes = [vp, vp, vp, i32, i32, i64, vp, vp, vp]
+    lib.dexct_sirt_update.argtypes = [vp, vp, vp, i64, f64, i32, vp]
     lib.dexct_label_moments.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     lib.dexct_sino_allgather.argtypes = [vp, vp, i64, vp, vp]
     lib.dexct_sino_gather.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i64), i32, i32, i32, vp, vp]

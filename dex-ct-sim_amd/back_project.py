@@ -84,12 +84,16 @@ def default_slices(ct):
     return ct.N_rows, -0.5 * (ct.N_rows - 1) * ct.h_iso, ct.h_iso
 
 
-def recon_device(sino_d, ct, N_matrix, FOV, ramp, window=None, slices=None, bhc=None):
+def recon_device(sino_d, ct, N_matrix, FOV, ramp, window=None, slices=None, bhc=None, method='fbp', n_iters=20, n_subsets=1,
+                 relax=1.0, init='fbp', nonneg=True, history=None):
     """sino_d: device float32 [N_proj, N_channels] or [N_proj, N_rows, N_channels] -> image tensor
     [N_matrix, N_matrix] or [N_rows, N_matrix, N_matrix] (float32, 1/cm).  A cone-beam scanner (``ct.cone``) is
     reconstructed with Feldkamp's algorithm onto ``slices = (n_slices, z_first [cm], dz [cm])``.  ``bhc``: a
     ``bhc.LinearizationTable`` - the sinogram is linearised first (into a new buffer; sino_d is left as it is), before
-    Parker's weights, which a nonlinear map must not follow."""
+    Parker's weights, which a nonlinear map must not follow.  ``method`` and the keywords after it: see get_recon."""
+    if method != 'fbp':
+        return _recon_iterative(sino_d, ct, N_matrix, FOV, ramp, window, bhc, method, n_iters, n_subsets, relax, init, nonneg,
+                                history)
     lib = _native.load()
     dev = sino_d.device
     three_d = sino_d.dim() == 3
@@ -140,14 +144,43 @@ def recon_device(sino_d, ct, N_matrix, FOV, ramp, window=None, slices=None, bhc=
     return img if three_d else img[0]
 
 
-def get_recon(sino, ct, spec, N_matrix, FOV, ramp, window=None, slices=None, bhc=None):
+def _recon_iterative(sino_d, ct, N_matrix, FOV, ramp, window, bhc, method, n_iters, n_subsets, relax, init, nonneg, history):
+    """SIRT / OS-SART of a fan or stacked-fan sinogram (iterative.py), from the FBP image or from zero."""
+    from . import iterative
+    n_subsets = iterative.check_options(method, ct, n_iters, n_subsets, relax, init)
+    three_d = sino_d.dim() == 3
+    s = (sino_d if three_d else sino_d[:, None, :]).contiguous()
+    n_views, n_rows, n_ch = s.shape
+    if n_views != ct.N_proj or n_ch != ct.N_channels:
+        raise ValueError(f'sinogram {tuple(sino_d.shape)} does not match the scanner ({ct.N_proj} x {ct.N_channels})')
+    proj = iterative.ImageProjector(ct, N_matrix, FOV, n_slices=n_rows)
+    if bhc is not None:
+        from .bhc import linearize_device
+        s = linearize_device(s, bhc)
+    x0 = recon_device(s, ct, N_matrix, FOV, ramp, window) if init == 'fbp' else None
+    img = iterative.sirt(s, proj, n_iters, n_subsets, relax, x0=x0, nonneg=nonneg, history=history)
+    return img if three_d else img[0]
+
+
+def get_recon(sino, ct, spec, N_matrix, FOV, ramp, window=None, slices=None, bhc=None, method='fbp', n_iters=20, n_subsets=1,
+              relax=1.0, init='fbp', nonneg=True, history=None):
     """Drop-in for ``recon_raw, recon_HU = get_recon(sino, ct, spec, N_matrix, FOV, ramp)`` (main.py:134).
     ``window``: apodisation of the ramp (WINDOWS; default ``DEXCT_FBP_WINDOW`` or the plain band-limited ramp).
     Cone-beam sinograms ([N_proj, N_rows, N_channels] of a ``cone=True`` scanner) are reconstructed with Feldkamp's
     algorithm into ``slices = (n_slices, z_first, dz)`` (default: default_slices).
     ``bhc``: beam-hardening correction of the log sinogram before the reconstruction (bhc.py) - a material ('water',
     'bone', a Material or (formula, density)) linearised for ``spec`` and the scanner's detector, or a prebuilt
-    ``bhc.LinearizationTable``.  recon_HU stays 1000 (raw - water_mu) / water_mu: water reads 0 HU after water BHC."""
+    ``bhc.LinearizationTable``.  recon_HU stays 1000 (raw - water_mu) / water_mu: water reads 0 HU after water BHC.
+    ``method``: 'fbp' (the default: everything above), 'sirt' or 'os-sart' - ``n_iters`` iterations of iterative.sirt on the
+    matched projector pair of the same grid, over ``n_subsets`` ordered subsets of the views (1: SIRT; more: OS-SART;
+    'os-sart' with the default of 1 means 10), relaxation ``relax`` in (0, 2), started from the FBP image (``init='fbp'``) or
+    from zero (``'zero'``), clamped at 0 after every update if ``nonneg``; ``history``: a list that receives the weighted
+    residual norm before each iteration.  Fan and stacked fan only.  The warning about non-finite values, ``bhc`` and the HU
+    formula are those of the FBP path.  A short scan needs no Parker weights here: the iteration solves A x = b for the views
+    there are, and a ray measured twice simply enters twice (the weights only serve init='fbp')."""
+    if method != 'fbp':
+        from . import iterative
+        iterative.check_options(method, ct, n_iters, n_subsets, relax, init, FOV)
     dev = device()
     sino_d = to_dev(np.asarray(sino, dtype=np.float32), torch.float32, dev)
     bad = int((~torch.isfinite(sino_d)).sum().item())
@@ -161,7 +194,11 @@ def get_recon(sino, ct, spec, N_matrix, FOV, ramp, window=None, slices=None, bhc
         from . import bhc as bhc_mod
         table = bhc if isinstance(bhc, bhc_mod.LinearizationTable) else bhc_mod.linearization_table(ct, spec, bhc)
         bhc_mod.linearize_device(sino_d, table, out=sino_d)         # sino_d is this call's own copy
-    raw = recon_device(sino_d, ct, N_matrix, FOV, ramp, window, slices).cpu().numpy()
+    if method != 'fbp':
+        raw = recon_device(sino_d, ct, N_matrix, FOV, ramp, window, None, None, method, n_iters, n_subsets, relax, init, nonneg,
+                           history).cpu().numpy()
+    else:
+        raw = recon_device(sino_d, ct, N_matrix, FOV, ramp, window, slices).cpu().numpy()
     mu_w = water_mu(ct, spec)
     return raw, (1000.0 * (raw - mu_w) / mu_w).astype(np.float32)
 

@@ -1,0 +1,225 @@
+"""Iterative reconstruction (SIRT / OS-SART) on a matched projector pair (csrc/iterative.hip; an extension: the reference
+reconstructs with filtered back-projection only).
+
+``ImageProjector`` applies the system matrix A of the label projector to a float32 image (``forward``) and its transpose to a
+sinogram (``adjoint``): dexct_image_project and dexct_image_backproject on the fixed-point plan of dexct_fan_plan, with the
+image grid of ``get_recon`` (``N_matrix`` pixels over ``FOV`` cm, centred on the isocentre) in the place of the phantom grid.
+Row i of A holds the intersection lengths [cm] of ray i with the pixels (include/dexct.h states the coefficients); both
+kernels form them with one device function, so <A x, y> = <x, A^T y> up to float32 rounding.
+
+``sirt`` iterates, for the ordered subsets s = 0 .. S - 1 of the views (subset s = the views congruent to s modulo S):
+
+    r_i = (b_i - (A x)_i) / R_i          R_i = sum_j a_ij      (0 for a ray that misses the grid)
+    x_j <- x_j + relax * (sum_{i in s} a_ij r_i) / C^s_j       C^s_j = sum_{i in s} a_ij   (pixels with C = 0 stay)
+    x_j <- max(x_j, 0)                                         if nonneg
+
+S = 1 is SIRT (Gilbert 1972; for relax in (0, 2) the R-weighted residual norm never increases), S > 1 is OS-SART (Andersen &
+Kak 1984 with ordered subsets).  Every step is a HIP kernel (dexct_sirt_residual, dexct_sirt_update); torch tensors are the
+device containers.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from . import _native
+from ._device import device, ptr, stream_ptr, to_dev
+
+METHODS = ('fbp', 'sirt', 'os-sart')
+OS_SART_SUBSETS = 10
+
+
+def check_options(method, ct, n_iters, n_subsets, relax, init='fbp', FOV=None):
+    """The argument checks of ``get_recon(..., method=)``, before any device access.  Returns the subset count."""
+    if method not in METHODS:
+        raise ValueError(f'unknown reconstruction method {method!r}; choose from {METHODS}')
+    if method == 'fbp':
+        return 1
+    if bool(getattr(ct, 'cone', False)):
+        raise ValueError('iterative reconstruction is fan and stacked-fan only: a cone-beam scanner has no matched pair here')
+    if FOV is not None and 0.5 * np.sqrt(2.0) * float(FOV) >= ct.SID:
+        raise ValueError(f'FOV = {FOV} cm: the image grid does not lie strictly inside the source circle (SID = {ct.SID} cm)')
+    if init not in ('fbp', 'zero'):
+        raise ValueError(f"init must be 'fbp' or 'zero', not {init!r}")
+    if int(n_iters) < 1:
+        raise ValueError(f'n_iters = {n_iters}: at least one iteration')
+    if not 0.0 < float(relax) < 2.0:
+        raise ValueError(f'relax = {relax} lies outside (0, 2)')
+    n_subsets = int(n_subsets)
+    if method == 'os-sart' and n_subsets == 1:
+        n_subsets = min(OS_SART_SUBSETS, ct.N_proj)
+    if not 1 <= n_subsets <= ct.N_proj:
+        raise ValueError(f'n_subsets = {n_subsets} lies outside 1 .. N_proj = {ct.N_proj}')
+    return n_subsets
+
+
+class ImageProjector:
+    """The pair (A, A^T) of one scanner and one image grid; the plan of all views is built once, on first use.
+
+    ``ImageProjector(ct, N_matrix, FOV, n_slices=1)``: the grid of ``get_recon``; ``n_slices`` stacked slices share the plan
+    (row r of the sinogram images slice r).  ``transposed=False`` makes both kernels work on the image alone, without the
+    in-plane transposed copy that the x-dominant rays otherwise use (tools/probes/iter_recon.py measures the two)."""
+
+    def __init__(self, ct, N_matrix, FOV, n_slices=1, transposed=True):
+        if bool(getattr(ct, 'cone', False)):
+            raise ValueError('ImageProjector is fan and stacked-fan only: a cone-beam scanner has no matched pair here')
+        n, fov = int(N_matrix), float(FOV)
+        if n < 1 or not fov > 0 or int(n_slices) < 1:
+            raise ValueError(f'N_matrix = {N_matrix}, FOV = {FOV}, n_slices = {n_slices}: positive values wanted')
+        self._setup(nx=n, ny=n, nz=int(n_slices), dx=fov / n, dy=fov / n, n_views=ct.N_proj, n_channels=ct.N_channels,
+                    n_rows=int(n_slices), z_first=0, sid=ct.SID, sdd=ct.SDD, view_cs=ct.view_cs(), chan_cs=ct.chan_cs(),
+                    transposed=transposed)
+
+    @classmethod
+    def from_grid(cls, nx, ny, nz, dx, dy, n_views, n_channels, n_rows, z_first, sid, sdd, view_cs, chan_cs, transposed=True):
+        """Any grid (nx != ny, dx != dy) and any window of slices: row r images slice ``z_first + r`` of ``nz``."""
+        self = cls.__new__(cls)
+        self._setup(nx=int(nx), ny=int(ny), nz=int(nz), dx=float(dx), dy=float(dy), n_views=int(n_views),
+                    n_channels=int(n_channels), n_rows=int(n_rows), z_first=int(z_first), sid=float(sid), sdd=float(sdd),
+                    view_cs=view_cs, chan_cs=chan_cs, transposed=transposed)
+        return self
+
+    def _setup(self, nx, ny, nz, dx, dy, n_views, n_channels, n_rows, z_first, sid, sdd, view_cs, chan_cs, transposed):
+        # the plan clips every ray against the grid from a source OUTSIDE it
+        if 0.5 * np.hypot(nx * dx, ny * dy) >= sid:
+            raise ValueError(f'the image grid ({nx * dx:.6g} x {ny * dy:.6g} cm, half diagonal {0.5 * np.hypot(nx * dx, ny * dy):.6g} '
+                             f'cm) does not lie strictly inside the source circle (SID = {sid:.6g} cm)')
+        if z_first < 0 or n_rows < 1 or z_first + n_rows > nz:
+            raise ValueError(f'rows {z_first} .. {z_first + n_rows - 1} lie outside the {nz} slices')
+        self.nx, self.ny, self.nz, self.n_views, self.n_channels, self.n_rows, self.z_first = nx, ny, nz, n_views, n_channels, n_rows, z_first
+        self.geom = _native.FanGeom(n_views, n_channels, n_rows, z_first, nx, ny, nz, 0, dx, dy, 1.0, sid, sdd)
+        self._view_cs, self._chan_cs = np.ascontiguousarray(view_cs, np.float64), np.ascontiguousarray(chan_cs, np.float64)
+        self.transposed = bool(transposed)
+        self.plan = None
+        self._row_sums, self._col_sums = None, {}
+
+    # ---- device state ---------------------------------------------------------------------------------------------------------
+    def _ready(self):
+        if self.plan is not None:
+            return
+        self.lib = _native.load()
+        self.dev = device()
+        vcs, ccs = to_dev(self._view_cs, torch.float64, self.dev), to_dev(self._chan_cs, torch.float64, self.dev)
+        plan = torch.empty(self.n_views * self.n_channels * _native.PLAN_BYTES, dtype=torch.uint8, device=self.dev)
+        _native.check(self.lib.dexct_fan_plan(C.byref(self.geom), ptr(vcs), ptr(ccs), 0, self.n_views, ptr(plan), stream_ptr()),
+                      'dexct_fan_plan')
+        torch.cuda.current_stream().synchronize()          # vcs and ccs may go once the plan is written
+        self.scratch = torch.empty(self.image_shape, dtype=torch.float32, device=self.dev) if self.transposed else None
+        self.plan = plan
+
+    @property
+    def image_shape(self):
+        return (self.nz, self.ny, self.nx)
+
+    @property
+    def sino_shape(self):
+        return (self.n_views, self.n_rows, self.n_channels)
+
+    def _views(self, views):
+        begin, end, step = (0, self.n_views, 1) if views is None else (int(v) for v in views)
+        if not (0 <= begin < end <= self.n_views and step >= 1):
+            raise ValueError(f'views = {views}: (begin, end, step) with 0 <= begin < end <= {self.n_views} and step >= 1 wanted')
+        return begin, end, step
+
+    def _tensor(self, t, shape, what):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError(f'{what}: a contiguous float32 device tensor wanted')
+        if t.numel() != int(np.prod(shape)):
+            raise ValueError(f'{what}: shape {tuple(t.shape)} does not match {shape}')
+        return t
+
+    def forward(self, img_d, views=None, out=None):
+        """A x: image [nz, ny, nx] ([ny, nx] for one slice) -> sinogram [n_views, n_rows, n_channels].  ``views = (begin, end,
+        step)``: only those views are computed; the other lines of ``out`` stay (zeros in a new tensor)."""
+        self._ready()
+        begin, end, step = self._views(views)
+        img = self._tensor(img_d, self.image_shape, 'image')
+        if out is None:
+            out = torch.zeros(self.sino_shape, dtype=torch.float32, device=self.dev)
+        sino = self._tensor(out, self.sino_shape, 'out')
+        st = stream_ptr()
+        if self.transposed:
+            _native.check(self.lib.dexct_transpose_batched(ptr(img), ptr(self.scratch), self.nz, self.ny, self.nx, 4, st),
+                          'dexct_transpose_batched')
+        line = self.n_rows * self.n_channels
+        _native.check(self.lib.dexct_image_project(
+            C.byref(self.geom), self.plan.data_ptr() + begin * self.n_channels * _native.PLAN_BYTES, begin, end, step, ptr(img),
+            ptr(self.scratch), sino.data_ptr() + 4 * begin * line, st), 'dexct_image_project')
+        return out
+
+    def adjoint(self, sino_d, views=None, out=None, accumulate=False):
+        """A^T y over the views -> image [nz, ny, nx]; ``out`` is overwritten unless ``accumulate``."""
+        self._ready()
+        begin, end, step = self._views(views)
+        sino = self._tensor(sino_d, self.sino_shape, 'sinogram')
+        if out is None:
+            out = torch.empty(self.image_shape, dtype=torch.float32, device=self.dev)
+            accumulate = False
+        img = self._tensor(out, self.image_shape, 'out')
+        line = self.n_rows * self.n_channels
+        _native.check(self.lib.dexct_image_backproject(
+            C.byref(self.geom), self.plan.data_ptr() + begin * self.n_channels * _native.PLAN_BYTES, begin, end, step,
+            sino.data_ptr() + 4 * begin * line, ptr(img), ptr(self.scratch), int(bool(accumulate)), stream_ptr()),
+            'dexct_image_backproject')
+        return out
+
+    def row_sums(self):
+        """R = A 1 (the forward kernel applied to an image of ones), cached."""
+        if self._row_sums is None:
+            self._ready()
+            self._row_sums = self.forward(torch.ones(self.image_shape, dtype=torch.float32, device=self.dev))
+        return self._row_sums
+
+    def col_sums(self, subset=0, n_subsets=1):
+        """C^s = A_s^T 1 over the views congruent to ``subset`` modulo ``n_subsets`` (the adjoint kernel applied to a sinogram
+        of ones), cached."""
+        key = (int(subset), int(n_subsets))
+        if key not in self._col_sums:
+            self._ready()
+            ones = torch.ones(self.sino_shape, dtype=torch.float32, device=self.dev)
+            self._col_sums[key] = self.adjoint(ones, views=(key[0], self.n_views, key[1]))
+        return self._col_sums[key]
+
+
+def sirt(sino_d, proj, n_iters, n_subsets=1, relax=1.0, x0=None, nonneg=True, history=None):
+    """``n_iters`` passes over the ``n_subsets`` ordered subsets (module docstring); sino_d: device float32 [n_views, n_rows,
+    n_channels]; x0: start image (default zeros; not modified).  ``history``: a list that receives the R-weighted residual
+    norm sqrt(sum (b - A x)_i^2 / R_i) of the image BEFORE each iteration (computed on the device; one host
+    synchronisation per iteration).  Returns the image [nz, ny, nx]."""
+    n_iters, S, relax = int(n_iters), int(n_subsets), float(relax)
+    if n_iters < 1 or not 1 <= S <= proj.n_views or not 0.0 < relax < 2.0:
+        raise ValueError(f'n_iters = {n_iters}, n_subsets = {S}, relax = {relax}: n_iters >= 1, 1 <= n_subsets <= '
+                         f'{proj.n_views} and 0 < relax < 2 wanted')
+    proj._ready()
+    lib, dev = proj.lib, proj.dev
+    b = proj._tensor(sino_d, proj.sino_shape, 'sinogram')
+    x = torch.zeros(proj.image_shape, dtype=torch.float32, device=dev) if x0 is None else \
+        proj._tensor(x0, proj.image_shape, 'x0').clone()
+    R = proj.row_sums()
+    ax = torch.zeros(proj.sino_shape, dtype=torch.float32, device=dev)
+    g = torch.empty(proj.image_shape, dtype=torch.float32, device=dev)
+    norm2 = torch.zeros(1, dtype=torch.float64, device=dev) if history is not None else None
+    line = proj.n_rows * proj.n_channels
+    n_views = proj.n_views
+
+    def residual(s, step, r, n2):
+        off = 4 * s * line
+        _native.check(lib.dexct_sirt_residual(b.data_ptr() + off, ax.data_ptr() + off, R.data_ptr() + off, n_views - s, step,
+                                              line, None if r is None else r.data_ptr() + off, ptr(n2), stream_ptr()),
+                      'dexct_sirt_residual')
+
+    for _ in range(n_iters):
+        if history is not None and S > 1:                  # (with one subset the iteration's own residual is the one wanted)
+            proj.forward(x, out=ax)
+            residual(0, 1, None, norm2)
+            history.append(float(np.sqrt(norm2.item())))
+        for s in range(S):
+            views = (s, n_views, S)
+            proj.forward(x, views=views, out=ax)
+            residual(s, S, ax, norm2 if S == 1 else None)
+            proj.adjoint(ax, views=views, out=g)
+            _native.check(lib.dexct_sirt_update(ptr(x), ptr(g), ptr(proj.col_sums(s, S)), x.numel(), relax, int(bool(nonneg)),
+                                                stream_ptr()), 'dexct_sirt_update')
+        if history is not None and S == 1:
+            history.append(float(np.sqrt(norm2.item())))
+    return x

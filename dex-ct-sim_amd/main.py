@@ -9,7 +9,8 @@ for every run in the parameter file, for every dual-energy spectrum pair:
   3. when ``back_project`` is set: reconstruct every log sinogram (:134 -> recon_raw/recon_HU .bin, :135-136)
      and both basis-material sinograms (:168 -> mat{1,2}_recon_float32.bin, :169); with ``--bhc water bone`` also the
      beam-hardening-corrected images of every log sinogram, ``recon_{water,bone}BHC_{raw,HU}_float32.bin`` (the files
-     the reference's plots.py:184-195 reads; basis-material sinograms are linear in thickness already and get none).
+     the reference's plots.py:184-195 reads; basis-material sinograms are linear in thickness already and get none);
+     ``--recon sirt`` reconstructs all of them iteratively (SIRT / OS-SART, iterative.py) instead of by FBP.
 
 Differences from the reference script, all on purpose: inputs are command-line options instead of
 edited source lines (:80-82, :101-103); figures are off unless --show; both spectra of a pair are
@@ -84,7 +85,13 @@ def main(argv=None):
     ap.add_argument('--bhc', nargs='*', default=[], choices=['water', 'bone'],
                     help='also write beam-hardening-corrected reconstructions of every log sinogram, linearised for '
                          'these reference materials (recon_<m>BHC_{raw,HU}_float32.bin beside recon_raw)')
+    ap.add_argument('--recon', default='fbp', choices=['fbp', 'sirt'],
+                    help='reconstruction method: filtered back-projection (default) or SIRT / OS-SART on the matched projector '
+                         'pair, started from the FBP image; the output file names stay the reference\'s')
+    ap.add_argument('--recon-iters', type=int, default=20, help='iterations of --recon sirt')
+    ap.add_argument('--recon-subsets', type=int, default=1, help='ordered subsets of --recon sirt (1: SIRT, more: OS-SART)')
     args = ap.parse_args(argv)
+    recon_kw = {} if args.recon == 'fbp' else dict(method=args.recon, n_iters=args.recon_iters, n_subsets=args.recon_subsets)
 
     import torch.distributed as dist
     if int(os.environ.get('WORLD_SIZE', '1')) > 1 and not dist.is_initialized():
@@ -124,11 +131,11 @@ def main(argv=None):
                     if do_bp:
                         print('Back projecting!')
                         spec = specs[0] if spec_id == s1 else specs[1]
-                        recon_raw, recon_HU = get_recon(sino_log, ct, spec, N_matrix, FOV, ramp, window=args.window)
+                        recon_raw, recon_HU = get_recon(sino_log, ct, spec, N_matrix, FOV, ramp, window=args.window, **recon_kw)
                         recon_raw.astype(np.float32).tofile(sub_dir + 'recon_raw_float32.bin')
                         recon_HU.astype(np.float32).tofile(sub_dir + 'recon_HU_float32.bin')
                         for m in dict.fromkeys(args.bhc):
-                            bhc_raw, bhc_HU = get_recon(sino_log, ct, spec, N_matrix, FOV, ramp, window=args.window, bhc=m)
+                            bhc_raw, bhc_HU = get_recon(sino_log, ct, spec, N_matrix, FOV, ramp, window=args.window, bhc=m, **recon_kw)
                             bhc_raw.astype(np.float32).tofile(sub_dir + f'recon_{m}BHC_raw_float32.bin')
                             bhc_HU.astype(np.float32).tofile(sub_dir + f'recon_{m}BHC_HU_float32.bin')
                         if args.show:
@@ -150,7 +157,9 @@ def main(argv=None):
                 if do_bp:
                     print('Back projecting basis material sinograms!')
                     for i, matsino in enumerate([matsino1, matsino2]):
-                        recon_raw, _ = get_recon(matsino, ct, specs[0], N_matrix, FOV, ramp, window=args.window)    # spec is filler (:168)
+                        # spec is filler (:168); basis-material line integrals may be negative: no clamp at 0
+                        mat_kw = dict(recon_kw, nonneg=False) if recon_kw else {}
+                        recon_raw, _ = get_recon(matsino, ct, specs[0], N_matrix, FOV, ramp, window=args.window, **mat_kw)
                         recon_raw.astype(np.float32).tofile(sub_dir + f'mat{i + 1}_recon_float32.bin')
                 print(f'matdecomp finished for {s1}-{s2} : t={time() - t0:.2f}s')
 

@@ -553,6 +553,48 @@ int dexct_label_moments(const float* m1, const float* m2, const uint8_t* labels,
 int dexct_bhc_linearize(const float* p, int64_t n, const float* table, int32_t log2_min, int32_t cells_log2,
                         int32_t octaves_pos, int32_t octaves_neg, float* out, void* stream);
 
+/* A matched projector pair on float32 images (csrc/iterative.hip): the system matrix A of the label projector applied to an
+ * image, and its transpose applied to a sinogram - the primitive of iterative reconstruction and of reprojection.
+ * geom: nx, ny, dx, dy describe the IMAGE grid, centred on the isocentre, pixel (ix, iy) at ((ix - nx/2 + 1/2) dx,
+ * (iy - ny/2 + 1/2) dy) - the grid of dexct_fbp_backproject with dx = dy = fov / n_matrix; image [nz][ny][nx] float32; row r
+ * of the stacked fan images slice z_first + r (z_first + n_rows <= nz) and all rows share the plan.  plan: as written by
+ * dexct_fan_plan for this geom from view_begin on, plan[(view - view_begin) * n_channels + channel].
+ * Row i = (view, row, channel) of A: for every dominant-axis slab s of the plan the fixed-point DDA gives the pieces (ja, t),
+ * (jb, 1 - t); a[i, (s, ja)] = t * len_per_u and a[i, (s, jb)] = (1 - t) * len_per_u (float32 products) where ja != jb, the
+ * single coefficient len_per_u where ja == jb, nothing for a piece whose minor index lies outside the grid.  Both entry
+ * points form the coefficients with one shared device function.
+ * Views: view_begin + k * view_step < view_end, k = 0, 1, ... (view_step >= 1; an ordered subset of OS-SART is view_begin =
+ * s, view_step = S); sino uses layout 0 of dexct_siddon_project, ((view - view_begin) * n_rows + row) * n_channels + channel,
+ * so it spans every view of [view_begin, view_end): the lines of the views in between are neither read nor written.
+ *   dexct_image_project:     sino[i] = sum_j a[i, j] image[j], float32, summed in slab order: one value per ray, no atomics,
+ *                            the same input gives bit-identical output.  image_t (may be NULL): the in-plane transposed copy
+ *                            [nz][nx][ny] of image (dexct_transpose_batched with batch nz, rows ny, cols nx), read by the rays
+ *                            whose dominant axis is x so that a wave's loads are contiguous; without it they read image.
+ *   dexct_image_backproject: image[j] (+)= sum_i a[i, j] sino[i] over the same views.  accumulate == 0: the whole image (nz
+ *                            slices) is zeroed inside the call first.  acc_t (may be NULL): scratch of nz * nx * ny float32,
+ *                            contents ignored and overwritten - the rays whose dominant axis is x accumulate into it
+ *                            transposed and one final pass adds it to image.  The sums are float atomics: their order is
+ *                            not fixed, so the result is reproducible to rounding, not bit for bit.
+ * DEXCT_EINVAL: a null geom, plan, image or sino, non-positive sizes, view_step < 1, an empty or out-of-range view range,
+ * slices outside the image; DEXCT_ERANGE: nx or ny above 8192 (the plan's limit), more than 65535 views in the range, rows or
+ * slices.  Every argument error is returned before the first launch. */
+int dexct_image_project(const dexct_fan_geom* geom, const dexct_ray_plan* plan, int32_t view_begin, int32_t view_end,
+                        int32_t view_step, const float* image, const float* image_t, float* sino, void* stream);
+int dexct_image_backproject(const dexct_fan_geom* geom, const dexct_ray_plan* plan, int32_t view_begin, int32_t view_end,
+                            int32_t view_step, const float* sino, float* image, float* acc_t, int32_t accumulate,
+                            void* stream);
+
+/* The element-wise steps of SIRT / OS-SART (dex-ct-sim_amd/iterative.py has the iteration).
+ *   dexct_sirt_residual: over lines k * line_step < n_lines of `line` values each (a line = one view: n_rows * n_channels),
+ *                        r = (b - ax) / row_sum where row_sum > 0, else 0 (a ray that misses the grid); r may be NULL or
+ *                        equal ax.  norm2 (may be NULL; not both NULL): one device float64, zeroed by the call, receives
+ *                        sum (b - ax)^2 / row_sum over the same elements (float64 atomics across workgroups).
+ *   dexct_sirt_update:   x += relax * (g / col_sum) where col_sum > 0 (other pixels stay), then x = max(x, 0) if nonneg; n
+ *                        values; relax > 0. */
+int dexct_sirt_residual(const float* b, const float* ax, const float* row_sum, int32_t n_lines, int32_t line_step,
+                        int64_t line, float* r, double* norm2, void* stream);
+int dexct_sirt_update(float* x, const float* g, const float* col_sum, int64_t n, double relax, int32_t nonneg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
