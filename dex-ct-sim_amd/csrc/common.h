@@ -58,8 +58,12 @@ __device__ __forceinline__ SlabPieces dda_slab(long long Va, long long SV, uint3
 
 // The second output of get_sino (main.py:120-122): ln(air / counts) in float32, as np.log(np.float32(air) / raw)
 // computes it: v_rcp_f32 and v_log_f32 (1 ulp each); counts == 0 gives +inf like the NumPy expression.
+// v_rcp_f32 takes a denormal operand for zero, which made +inf of a quotient NumPy still represents (counts of 0.9e-38 under an
+// air signal below 4: tests/test_gpu_detect.py): counts below 2^-100 are scaled by 2^64 - exact - and the quotient is scaled
+// back, where it overflows to +inf exactly when air / c does.  Every other count is multiplied by 1: the same bits as before.
 __device__ __forceinline__ float log_ratio(float air, float c) {
-  return __builtin_amdgcn_logf(air * __builtin_amdgcn_rcpf(c)) * 0.693147180559945309f;
+  const float k = c < 0x1p-100f ? 0x1p64f : 1.0f;
+  return __builtin_amdgcn_logf(air * __builtin_amdgcn_rcpf(c * k) * k) * 0.693147180559945309f;
 }
 
 }  // namespace dexct

@@ -82,7 +82,12 @@ typedef struct dexct_ray_plan {
  * get_recon reconstructs, main.py:134): sino_log[s*n_rays + ray] = ln(air[s] / counts[s*n_rays + ray]) in float32, written
  * by the projection's own detection store in the ray order of counts.  air[s] = sum_e weights[s*n_energies + e], the
  * unattenuated signal.  Pass NULL (or a NULL sino_log) when the log sinogram is not wanted.  Not together with a
- * variance output (DEXCT_EINVAL): the log of a noisy sinogram is taken after dexct_add_noise, by dexct_sino_log. */
+ * variance output (DEXCT_EINVAL): the log of a noisy sinogram is taken after dexct_add_noise, by dexct_sino_log.
+ * Contract (every form that writes it, dexct_sino_log and dexct_transpose_log included; tests/test_gpu_detect.py): where the
+ * float32 quotient air / counts is finite, |sino_log - ln(air / counts)| <= 2^-22 (1 + |ln(air / counts)|); where it is not -
+ * counts == 0, a noise-free ray that lost every energy (see counts below), or a quotient beyond the float32 range - exactly
+ * +inf, as np.log(np.float32(air) / counts) gives; never NaN for air > 0 and counts >= 0.  A SAMPLED ray is clipped at 1e-20
+ * (dexct_noise, dexct_add_noise), so the log of a noisy sinogram is finite everywhere. */
 typedef struct dexct_log_out {
   float* sino_log;              /* device, n_spectra * n_rays float32 */
   float air[DEXCT_MAX_SPECTRA]; /* host values, copied into the launch arguments */
@@ -139,6 +144,13 @@ int dexct_fan_plan(const dexct_fan_geom* geom, const double* view_cs, const doub
  *   weights[s*n_energies + e] effective spectrum of spectrum s (I0 * detector response * dE,
  *                             the weighting of matdecomp.py:146-150)
  *   counts[s*n_rays + ray]    (float32), n_rays = n_local_views*n_rows*n_channels
+ *             = sum_e weights[s][e] t_e, t_e = exp(-P_e), P_e = sum_m mu[m][e] pathlen[ray][m].  Contract of every
+ *             projection entry point of this header, for the counts and (with weights2 in the place of weights) the
+ *             variance, against the float64 sum over the float32 path lengths and tables (u = 2^-24, M = n_materials;
+ *             derivation in tests/detect_refs.py, enforced per ray by tests/test_gpu_detect.py):
+ *               |counts - exact| <= u sum_e |weights[s][e]| t_e ((M + 3.5) P_e + 2 + n_energies) + 2^-125 sum_e |weights[s][e]|
+ *             finite and, for non-negative weights, never negative.  An exponential below 2^-126 counts as zero (v_exp_f32
+ *             returns no denormals): a noise-free ray whose every energy is that dark has counts == 0 and a log of +inf.
  *   pathlen (optional, may be NULL): [ray][n_materials] float32 path length [cm] per material
  *   layout 0: ray = ((view - view_begin)*n_rows + row)*n_channels + channel   (the reference's
  *             [N_proj, N_channels] order per row; native to the ray-parallel kernel)

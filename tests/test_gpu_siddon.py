@@ -3,7 +3,11 @@
 bit-exact: plan table, voxel-index sequences, float32 piece lengths, per-material path lengths
            (vs the DDA form of the oracle, which mirrors the kernel arithmetic and is itself pinned
            against the float64 textbook Siddon in test_siddon_oracle.py)
-1e-5 rel : sinogram counts vs the float64 textbook Siddon + float64 detection (north-star tolerance)
+1e-5 rel : sinogram counts vs the float64 textbook Siddon + float64 detection (north-star tolerance).  The figure holds for
+           the thin phantoms used here (exponents of a few units): a float32 exponent carries an error proportional to
+           itself, and a correct kernel passes 1e-5 from an exponent of about 60 on.  The general, per-ray bound over the
+           dynamic range - through the underflow of the exponential to rays that lose every energy - is derived in
+           tests/detect_refs.py and enforced by tests/test_gpu_detect.py.
 """
 import ctypes
 
