@@ -16,7 +16,7 @@ SYMBOLS = ['dexct_strerror', 'dexct_abi_version', 'dexct_last_hip_error', 'dexct
            'dexct_siddon_project_grouped_packed', 'dexct_poisson_detect', 'dexct_vmi', 'dexct_label_moments', 'dexct_fdk_backproject', 'dexct_sino_allgather', 'dexct_sino_gather', 'dexct_transpose_log', 'dexct_host_pin', 'dexct_host_touch', 'dexct_host_unpin', 'dexct_download',
            'dexct_volume_ids', 'dexct_volume_remap', 'dexct_fbp_parker', 'dexct_sino_log', 'dexct_cone_layout_groups', 'dexct_cone_project_grouped',
            'dexct_bhc_linearize', 'dexct_image_project', 'dexct_image_backproject', 'dexct_sirt_residual', 'dexct_sirt_update',
-           'dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes']
+           'dexct_gn_reduced_rows', 'dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes']
 
 
 class FanGeom(C.Structure):
@@ -62,7 +62,9 @@ class GnOptions(C.Structure):
 
 
 GN_PASS_COUNT, GN_PASS_SHORTCUT = 1, 2
-GN_FLAG_FULL_LOOP, GN_FLAG_NATURAL_ORDER, GN_FLAG_ONE_STEP = 1, 2, 4
+GN_FLAG_FULL_LOOP, GN_FLAG_NATURAL_ORDER, GN_FLAG_ONE_STEP, GN_FLAG_FULL_RESIDUAL = 1, 2, 4, 8
+GN_REDUCED_HEADER = 16   # DEXCT_GN_REDUCED_HEADER
+GN_TABLE_ROW = 14        # doubles per energy row of the Newton tables (csrc/gn.hip, kTab)
 
 
 def gn_options(stop_tol=None, out_rows=0, out_channels=0, kernel=0, gn_pass=0, iterations=None, start=None, flags=0,
@@ -74,6 +76,23 @@ def gn_options(stop_tol=None, out_rows=0, out_channels=0, kernel=0, gn_pass=0, i
     o = GnOptions(-1.0 if stop_tol is None else float(stop_tol), int(out_rows), int(out_channels), int(kernel), int(gn_pass),
                   iterations, start, int(flags), int(blocks_per_cu))
     return C.byref(o)
+
+
+def gn_reduced_rows(mus, nodes, w):
+    """dexct_gn_reduced_rows on host arrays: the block (NumPy float64) a reduced residual rule adds to the device copy of a start
+    array - header of GN_REDUCED_HEADER doubles, then the kept rows in the format of the Newton tables."""
+    import numpy as np
+    lib = load()
+    mus = np.ascontiguousarray(mus, dtype=np.float64)
+    nodes = np.ascontiguousarray(nodes, dtype=np.int32)
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if mus.ndim != 2 or mus.shape[0] != 2 or w.shape != (2, nodes.size):
+        raise ValueError('mus must be [2, nE] and w [2, len(nodes)]')
+    block = np.zeros(GN_REDUCED_HEADER + GN_TABLE_ROW * nodes.size)
+    w0, w1 = np.ascontiguousarray(w[0]), np.ascontiguousarray(w[1])
+    check(lib.dexct_gn_reduced_rows(mus.ctypes.data, mus.shape[1], nodes.ctypes.data, nodes.size, w0.ctypes.data, w1.ctypes.data,
+                                    block.ctypes.data, block.size), 'dexct_gn_reduced_rows')
+    return block[:int(block[9])]
 
 
 PLAN_BYTES = 40   # sizeof(dexct_ray_plan)
@@ -158,6 +177,7 @@ def load():
     lib.dexct_gn_apply_mask.argtypes = [vp, i32, i64, f64, vp, vp]
     lib.dexct_gn_model_sums.argtypes = [vp, i64, vp, vp, i32, vp, vp, vp, vp]
     lib.dexct_reduce_max.argtypes = [vp, i32, i64, vp, vp]
+    lib.dexct_gn_reduced_rows.argtypes = [vp, i32, vp, i32, vp, vp, vp, i64]
     for name in SYMBOLS[3:-2]:
         getattr(lib, name).restype = C.c_int
     _lib = lib

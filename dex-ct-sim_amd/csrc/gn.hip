@@ -14,8 +14,9 @@
 // v_fma_f64 and costs neither LDS bandwidth nor VGPRs.  The only per-lane lookup is the 2048-entry
 // 2^(j/2048) table of the exponential, which sits in LDS (16 KB).
 // There is no dense contraction: the kernel is bound by the FP64 vector rate (FMA + exp), not by
-// HBM (8 B read + 16 B written per pixel); per energy-iteration it issues 25 FP64 instructions
-// (2 exponent, 2 clip, 9 exp, 12 accumulate).
+// HBM (8 B read + 16 B written per pixel); per energy a full Newton step issues 23 - 25 vector instructions (2 exponent, 0 - 2
+// clip, 9 exp, 12 accumulate), the chord step of the short cut 13 - 16 (2 accumulate; profiles/r07_gn_tile.md) - and sums
+// over the rows of a reduced residual rule where the start array carries one (kRedHeader below).
 #include <cstdlib>
 #include <type_traits>
 
@@ -870,6 +871,15 @@ __device__ __forceinline__ bool gn_exit_or_advance(double n0, double n1, int n_i
 // ratios), kappa |a| is 100 on average, eps 2e-8 at the median point (2e-7 / 1e-5 at the 90th / 99th percentile: it shrinks and
 // grows with d1): ~99 % of the plane passes with orders to spare, the rest takes full Newton steps.
 constexpr int kStartHeader = 12;
+// THE REDUCED RESIDUAL RULE (round 8; include/dexct.h, dexct_gn_reduced_rows; quadrature.residual_rule).  The chord step needs nu_k
+// at start values that all lie on the surface the table tabulates, and over that surface the columns exp(-a . mu(e)) of the
+// energies are numerically dependent: a subset of the energies with new weights reproduces both sums to rounding.  Where the host
+// has found and verified such a rule the start array says [10] = 3 and carries, behind the power form, a block of
+// kRedHeader doubles ([0] rows, [1..6] an EnergyClasses' counts, [7], [8] its clip-free maxima) and the rows in kTab format (weights
+// in slots 2 and 8); gn_shortcut_kernel<1> hands chord_residuals_f64 those rows instead of the workspace's.  Everything else
+// (the drain's Newton steps, STEPS == 2, the other kernels) sums over the full tables.
+constexpr int kRedHeader = 16;
+constexpr int kFlagReduced = 8;       // kernel flag of gn_shortcut_kernel<1>: use the block if the start array has one
 #ifndef DEXCT_GN_INTERP_UNROLL
 #define DEXCT_GN_INTERP_UNROLL 2      // rows of the 6 x 6 interpolation per loop trip (A/B: tools/probes/build_variant.sh)
 #endif
@@ -1016,7 +1026,7 @@ __device__ __forceinline__ void gn_cell_pairs(const double* __restrict__ start, 
   typedef double d2 __attribute__((ext_vector_type(2)));
   const int n = (int)start[3];
   const d2* __restrict__ cells = reinterpret_cast<const d2*>(start + kStartHeader) + (n + 1) * (n + 1);
-  const d2 ke = start[10] == 2.0 ? (cells + n * n)[idx] : d2{__builtin_huge_val(), __builtin_huge_val()};
+  const d2 ke = (start[10] == 2.0 || start[10] == 3.0) ? (cells + n * n)[idx] : d2{__builtin_huge_val(), __builtin_huge_val()};
   radius = cells[idx].y;
   kappa = ke.x;
   eps = ke.y;
@@ -1248,6 +1258,20 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_shortcut_kernel(const void* __
   __syncthreads();                        // the only barrier: waves work independently from here on
   const EnergyClasses ec{(int)ws[1], (int)ws[4], (int)ws[2], (int)ws[5], (int)ws[3], (int)ws[6], ws[7], ws[8]};
   const double* __restrict__ tab = ws + kWsHeader;
+  // the rows the chord residual sums over: the reduced rule's if the start array carries one (wave-uniform, read once)
+  const double* __restrict__ res_tab = tab;
+  EnergyClasses res_ec = ec;
+  if (STEPS == 1) {
+    int res_rows = n_e;
+    if ((flags & kFlagReduced) != 0 && start[10] == 3.0) {
+      const int nc = (int)start[3];
+      const double* __restrict__ blk = start + ((int)start[11] + 72 * nc * nc);
+      res_rows = (int)blk[0];
+      res_ec = EnergyClasses{(int)blk[1], (int)blk[2], (int)blk[3], (int)blk[4], (int)blk[5], (int)blk[6], blk[7], blk[8]};
+      res_tab = blk + kRedHeader;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *counter(13) = (unsigned long long)res_rows;     // (diagnostic: last_gn_stats)
+  }
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   d2* __restrict__ my_out = lds_out[wv];
   long long* __restrict__ snp = lds_snp[wv];
@@ -1375,7 +1399,7 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_shortcut_kernel(const void* __
         double n0 = s0, n1 = s1, m0 = s0, m1 = s1;
         if (STEPS == 1) {                                                    // from s to m: the chord step (chord_residuals_f64)
           double c[2];
-          chord_residuals_f64(tab, lds_pow, ec, gd0, gd1, s0, s1, c);
+          chord_residuals_f64(res_tab, lds_pow, res_ec, gd0, gd1, s0, s1, c);
           // m = s + B c with B_p0 = Bx_p - t Bt_p, B_p1 = Bt_p (gn_start<DERIV>)
           const double ct = fma(-cl.t, c[0], c[1]);
           m0 = s0 + fma(cl.Bx[0], c[0], cl.Bt[0] * ct);
@@ -1637,11 +1661,12 @@ struct GnEnv {
   long long coop_below;     // DEXCT_GN_COOP_BELOW=<pixels>
   int sort;                 // DEXCT_GN_SORT=0: natural order of the hand-out on small sinograms
   int tiles_per_fetch;      // DEXCT_GN_TILES_PER_FETCH=<n>: queue positions per reservation (0: by size)
+  int reduced;              // DEXCT_GN_REDUCED=0: the chord residual over the full tables (DEXCT_GN_FLAG_FULL_RESIDUAL on every call)
 };
 
 static const GnEnv& gn_env() {
   static const GnEnv env = [] {
-    GnEnv e{0, DEXCT_GN_DEFAULT_STOP_TOL, 0, kCoopBelowDefault, 1, 0};
+    GnEnv e{0, DEXCT_GN_DEFAULT_STOP_TOL, 0, kCoopBelowDefault, 1, 0, 1};
     auto flag = [](const char* name, char c) { const char* v = getenv(name); return v && v[0] == c; };
     auto number = [](const char* name, long long lo, long long hi, long long dflt) {
       const char* v = getenv(name);
@@ -1662,6 +1687,7 @@ static const GnEnv& gn_env() {
     e.coop_below = number("DEXCT_GN_COOP_BELOW", 0, 1ll << 62, kCoopBelowDefault);
     e.sort = !flag("DEXCT_GN_SORT", '0');
     e.tiles_per_fetch = (int)number("DEXCT_GN_TILES_PER_FETCH", 1, 1024, 0);
+    e.reduced = !flag("DEXCT_GN_REDUCED", '0');
     return e;
   }();
   return env;
@@ -1763,8 +1789,9 @@ int dexct_gn_decompose(const void* g1, const void* g2, int32_t g_is_f64, int64_t
   if (pass == DEXCT_GN_PASS_SHORTCUT && (!options->start || options->iterations)) return DEXCT_EINVAL;
   const double* start = (pass == DEXCT_GN_PASS_SHORTCUT) ? options->start : nullptr;
   if (start && (reinterpret_cast<uintptr_t>(start) & 15u)) return DEXCT_EINVAL;   // its pairs are read with 16-byte loads
-  if (options && (options->flags & ~(DEXCT_GN_FLAG_FULL_LOOP | DEXCT_GN_FLAG_NATURAL_ORDER | DEXCT_GN_FLAG_ONE_STEP))) return DEXCT_EINVAL;
+  if (options && (options->flags & ~(DEXCT_GN_FLAG_FULL_LOOP | DEXCT_GN_FLAG_NATURAL_ORDER | DEXCT_GN_FLAG_ONE_STEP | DEXCT_GN_FLAG_FULL_RESIDUAL))) return DEXCT_EINVAL;
   if (options && (options->flags & DEXCT_GN_FLAG_ONE_STEP) && pass != DEXCT_GN_PASS_SHORTCUT) return DEXCT_EINVAL;
+  if (options && (options->flags & DEXCT_GN_FLAG_FULL_RESIDUAL) && !(options->flags & DEXCT_GN_FLAG_ONE_STEP)) return DEXCT_EINVAL;
   if (options && options->blocks_per_cu < 0) return DEXCT_EINVAL;
   hipStream_t st = as_stream(stream);
   double* ws = reinterpret_cast<double*>(workspace);
@@ -1838,7 +1865,8 @@ int dexct_gn_decompose(const void* g1, const void* g2, int32_t g_is_f64, int64_t
                          (const double*)ws, n_energies, n_iters, tl, mask_max, mask_frac, kflags, tol, out_a, counters, options->iterations);
     else if (pass == DEXCT_GN_PASS_SHORTCUT && (oflags & DEXCT_GN_FLAG_ONE_STEP))
       hipLaunchKernelGGL(gn_shortcut_kernel<1>, dim3((unsigned)nb), block, 0, st, g1, g2, g_is_f64, (long long)n_pix,
-                         (const double*)ws, n_energies, n_iters, tl, mask_max, mask_frac, kflags, tol, out_a, counters, start);
+                         (const double*)ws, n_energies, n_iters, tl, mask_max, mask_frac,
+                         kflags | ((env.reduced && !(oflags & DEXCT_GN_FLAG_FULL_RESIDUAL)) ? kFlagReduced : 0), tol, out_a, counters, start);
     else if (pass == DEXCT_GN_PASS_SHORTCUT)
       hipLaunchKernelGGL(gn_shortcut_kernel<2>, dim3((unsigned)nb), block, 0, st, g1, g2, g_is_f64, (long long)n_pix,
                          (const double*)ws, n_energies, n_iters, tl, mask_max, mask_frac, kflags, tol, out_a, counters, start);
@@ -1867,6 +1895,48 @@ int dexct_gn_model_sums(const double* a, int64_t n_states, const double* i0, con
   hipLaunchKernelGGL(gn_model_sums_kernel, dim3((unsigned)nblk), dim3(256), 0, as_stream(stream), a, (long long)n_states, i0, mus,
                      n_energies, nu_out, g_out, s_out);
   DEXCT_LAUNCH_CHECK();
+  return DEXCT_OK;
+}
+
+int dexct_gn_reduced_rows(const double* mus, int32_t n_energies, const int32_t* nodes, int32_t n_nodes, const double* w0,
+                          const double* w1, double* block, int64_t block_len) {
+  if (!mus || !nodes || !w0 || !w1 || !block || n_energies <= 0 || n_nodes <= 0) return DEXCT_EINVAL;
+  if (block_len < (int64_t)kRedHeader + (int64_t)kTab * n_nodes) return DEXCT_EINVAL;
+  for (int j = 0; j < n_nodes; ++j) {
+    if (nodes[j] < 0 || nodes[j] >= n_energies) return DEXCT_EINVAL;
+    if (!(fabs(w0[j]) < __builtin_huge_val()) || !(fabs(w1[j]) < __builtin_huge_val())) return DEXCT_EINVAL;
+  }
+  for (int64_t i = 0; i < (int64_t)kRedHeader + (int64_t)kTab * n_nodes; ++i) block[i] = 0.0;
+  // the classes and their always-clipped heads as gn_tables_kernel sorts the full tables (kMuFree = 4 cm^2/g)
+  const double kMuFree = 4.0;
+  int n = 0, n_cls[3] = {0, 0, 0}, n_clip[3] = {0, 0, 0};
+  double m0f = 0.0, m1f = 0.0;
+  for (int cls = 0; cls < 3; ++cls) {
+    for (int part = 0; part < 2; ++part) {
+      for (int j = 0; j < n_nodes; ++j) {
+        const int e = nodes[j];
+        const double m0 = mus[e], m1 = mus[n_energies + e];
+        const bool z0 = w0[j] == 0.0, z1 = w1[j] == 0.0;
+        const int c = (!z0 && !z1) ? 0 : (!z0 ? 1 : (!z1 ? 2 : 3));
+        const bool big = !(fmax(fabs(m0), fabs(m1)) <= kMuFree);
+        if (c != cls || big != (part == 0)) continue;
+        double* t = block + kRedHeader + (size_t)n * kTab;
+        t[0] = -m0 * kExpScale;
+        t[1] = -m1 * kExpScale;
+        t[2] = w0[j];
+        t[8] = w1[j];
+        ++n;
+        ++n_cls[cls];
+        if (big) ++n_clip[cls];
+        else { m0f = fmax(m0f, fabs(m0)); m1f = fmax(m1f, fabs(m1)); }
+      }
+    }
+  }
+  block[0] = (double)n;
+  for (int cls = 0; cls < 3; ++cls) { block[1 + 2 * cls] = (double)n_cls[cls]; block[2 + 2 * cls] = (double)n_clip[cls]; }
+  block[7] = m0f;
+  block[8] = m1f;
+  block[9] = (double)(kRedHeader + kTab * n);
   return DEXCT_OK;
 }
 

@@ -148,6 +148,7 @@ _last_events = []      # (before, after) events of the launches of the most rece
 _last_zeroed = None
 _last_mode = 'single'
 _last_audit = None
+_last_ne = 0
 _table_cache = {}
 
 
@@ -157,11 +158,15 @@ def last_gn_stats():
     actually executed (the exits end pixels before n_iters; masked air pixels run none), ``stalled_lane_steps`` = lane-steps
     a wave could not hand out because all its result slots waited for stragglers.  0 for the mixed-precision and
     per-channel-spectrum kernels, which do not count.  ``mode``: 'one' / 'start' (the short cut), 'single', or 'exact (ill-posed
-    pair)'; ``audit``: the last sampled audit, if any."""
+    pair)'; ``audit``: the last sampled audit, if any.  ``residual_energies``: the table rows the chord residual of the one-step
+    launch summed per pixel, as the kernel reports it - the rows of the reduced residual rule where one is installed and not
+    switched off, else (and in every other mode) the tables' n_e."""
     if not _last_ws:
         return None
-    words = torch.stack([w[72:104].view(torch.int64) for w in _last_ws]).sum(dim=0).tolist()
-    st = {'pixel_iterations': int(words[0]), 'stalled_lane_steps': int(words[3]), 'launches': len(_last_ws), 'mode': _last_mode}
+    stacked = torch.stack([w[72:112].view(torch.int64) for w in _last_ws])
+    words = stacked[:, :4].sum(dim=0).tolist()
+    st = {'pixel_iterations': int(words[0]), 'stalled_lane_steps': int(words[3]), 'launches': len(_last_ws), 'mode': _last_mode,
+          'residual_energies': int(stacked[:, 4].max().item()) if _last_mode == 'one' else int(_last_ne)}
     if _last_events:
         torch.cuda.synchronize()
         st['main_ms'] = sum(e[0].elapsed_time(e[1]) for e in _last_events)
@@ -331,6 +336,35 @@ def power_form(start):
     return out
 
 
+def reduced_block(start, rule, mus):
+    """The device start array ``start`` (with its power form, [10] = 2) with the rows of a reduced residual rule appended behind
+    the power form and [10] set to 3 (csrc/gn.hip, kRedHeader; include/dexct.h): what gn_shortcut_kernel<1> then sums its chord
+    residual over.  Everything before the appended block is unchanged."""
+    n = int(start[3].item())
+    off = int(start[11].item()) + 72 * n * n
+    if not (start[10].item() == 2.0 and start[11].item() > 0.0 and off == start.numel()):
+        raise ValueError('reduced_block needs a start array that ends with its power form')
+    block = _native.gn_reduced_rows(_host_tables(mus), rule['nodes'], rule['w'])
+    out = torch.cat([start, torch.as_tensor(block, dtype=torch.float64).to(start.device)])
+    out[10] = 3.0
+    return out
+
+
+def _residual_rule(i0_h, mus_h, start_h, stats):
+    """(rule | None, info, source) of quadrature.residual_rule for these tables: from the rule's own file in the cache directory
+    (validated on load), else built (a second of host NumPy) and stored there."""
+    from . import quadrature
+    i0_2 = i0_h.reshape(2, -1)
+    path = quadrature.rule_cache_path(_cache_dir(), i0_2, mus_h, start_h) if start_h is not None else None
+    got = quadrature.rule_from_disk(path, i0_2.shape[1])
+    if got is not None:
+        return got[0], got[1], 'disk'
+    rule, info = quadrature.residual_rule(start_h, i0_2, mus_h, stats)
+    if start_h is not None:
+        quadrature.rule_to_disk(path, rule, info)
+    return rule, info, 'built'
+
+
 def _device_tables(i0, mus, dev, want_gate, cal_tol=1.0e-12):
     """(i0_d [2, nBins, nE], mus_d [2, nE], gate) for host or device tables, cached by content; ``want_gate``: prepare the short
     cut - gate = {'start': device array | None, 'ill_posed': bool, 'stats': ...} (None when not wanted); ``cal_tol``: the
@@ -369,6 +403,13 @@ def _device_tables(i0, mus, dev, want_gate, cal_tol=1.0e-12):
             gate['ill_posed'] = bool(quadrature.pair_is_ill_posed(stats))
             if start_h is not None and not gate['ill_posed'] and stats.get('open_share', 0.0) >= 0.1:
                 gate['start'] = power_form(to_dev(start_h, torch.float64, dev))
+                # the reduced residual rule of the chord step (quadrature.residual_rule): its rows go behind the power form of
+                # the DEVICE copy; the host table and its file are what they were
+                rule, info, src = _residual_rule(i0_h, mus_h, start_h, stats)
+                gate['stats'] = dict(stats, residual_rule=dict(info, source=src))
+                if rule is not None:
+                    gate['start'] = reduced_block(gate['start'], rule, mus_h)
+                    gate['rule'] = rule
         ent[('gate', cal_tol)] = gate
     return ent['i0'], ent['mus'], (ent.get(('gate', cal_tol)) if want_gate else None)
 
@@ -425,7 +466,7 @@ def _audit(g1, g2, a, i0, mus, n_iters, ppm, strict, out_rc, mask_max, mask_frac
 
 def gn_device(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=None, bin_div=1, mask_max=None,
               mask_frac=0.95, stop_tol=None, out_rc=None, kernel=0, accumulate_stats=False, two_level=None, full_loop=False,
-              natural_order=False, blocks_per_cu=0, audit=None, audit_strict=None):
+              natural_order=False, blocks_per_cu=0, audit=None, audit_strict=None, reduced=None):
     """g1, g2: device tensors of equal shape; mus: [2, nE] float64; i0: [2, nE] (one spectrum for all
     pixels) or [2, nBins, nE] (pixel p uses row (p // bin_div) % nBins: the reference's general layout).
     ``mask_max``: device float64 scalar (the global maximum of sinogram 1) - pixels with g1 >= mask_frac * max are
@@ -438,6 +479,9 @@ def gn_device(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=N
     ``full_loop``, ``natural_order``, ``blocks_per_cu``: dexct_gn_options.flags / .blocks_per_cu (checking and tuning: results do
     not depend on the last two, and on the first only through stop_tol = 0).  ``audit`` (pixels per million; None =
     DEFAULT_AUDIT_PPM), ``audit_strict``: the sampled audit of the short cut (see DEFAULT_AUDIT_PPM).
+    ``reduced``: None / True = the chord step of mode 'one' sums its residual over the reduced residual rule where one is installed
+    for the pair (quadrature.residual_rule), False = over all energies (so does DEXCT_GN_REDUCED=0 in the environment, read once by
+    the library); last_gn_stats()['residual_energies'] says which it was.
     Returns a device tensor of shape g1.shape + (2,) float64 (with ``out_rc``: the last two sinogram dimensions swapped)."""
     lib = _native.load()
     dev = g1.device
@@ -487,15 +531,17 @@ def gn_device(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=N
     a = out if out is not None else torch.empty(shape + (2,), dtype=torch.float64, device=dev)
     if out is not None and (a.numel() != 2 * g1.numel() or a.dtype != torch.float64 or not a.is_contiguous()):
         raise ValueError('out must be a contiguous float64 tensor with two values per pixel')
-    global _last_zeroed, _last_ws, _last_events, _last_mode, _last_audit
+    global _last_zeroed, _last_ws, _last_events, _last_mode, _last_audit, _last_ne
+    _last_ne = n_e
     is64 = int(g1.dtype == torch.float64)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     ws = torch.empty(lib.dexct_gn_workspace_bytes(n_e, n_bins), dtype=torch.uint8, device=dev)
-    ws[72:104].zero_()       # executed-iteration, progress, queue and stall counters: defined before anybody polls them
+    ws[72:112].zero_()       # executed-iteration, progress, queue and stall counters (and the residual's row count): defined before anybody polls them
     _last_zeroed = torch.cuda.Event()
     _last_zeroed.record()    # a progress poller on another stream waits for this (never reads uninitialised bytes)
     flags = ((_native.GN_FLAG_FULL_LOOP if full_loop else 0) | (_native.GN_FLAG_NATURAL_ORDER if natural_order else 0)
-             | (_native.GN_FLAG_ONE_STEP if mode == 'one' else 0))
+             | (_native.GN_FLAG_ONE_STEP if mode == 'one' else 0)
+             | (_native.GN_FLAG_FULL_RESIDUAL if mode == 'one' and reduced is False else 0))
     if start is not None:
         opts = _native.gn_options(stop_tol, rows, chans, 1, _native.GN_PASS_SHORTCUT, None, start.data_ptr(), flags, blocks_per_cu)
     else:

@@ -610,3 +610,309 @@ def validate_start(start, pieces, steps, roots):
     onestep[~np.isfinite(kappa), 1] = np.inf
     kappa[~np.isfinite(onestep[:, :, 1])] = np.inf
     return out, float(np.isfinite(cells[:, :, 0]).mean()), int(bad.sum())
+
+
+# ---- THE REDUCED RESIDUAL RULE of the chord step (csrc/gn.hip, kRedHeader; include/dexct.h, dexct_gn_reduced_rows) -----------------
+# The chord step of the short cut needs nu_k(s) = sum_e i0_k(e) exp(-(s0 mu0(e) + s1 mu1(e))) to float64 accuracy, but only at
+# start values s the gate table produces: interpolants of its tabulated fixed points over the cells that are open for the
+# one-step acceptance.  Over that domain the columns exp(-s . mu(e)) are numerically dependent - the singular values of the
+# row-normalised matrix fall below 1e-15 of the first after ~40 of 136 - so a SUBSET J of the energies with new weights
+# reproduces both sums to rounding: an interpolative decomposition.  A column-pivoted QR of the stacked, row-normalised matrices
+# of both measurements (block k: K diag(i0_k), each row divided by nu_k, K = exp(-s . mu)) picks J; with A P = Q [R11 R12] the
+# other columns are A[:, J] R11^-1 R12, so the sum over ALL columns is A[:, J] X 1 with X = [I, R11^-1 R12], and the weights of
+# measurement k are w_k = i0_k[J] * (X 1): exactly 0 where measurement k has no weight.
+# The node count is not fixed in advance: it is the smallest even count whose largest relative error - float64 against a long-double
+# sum of all energies, on verification points the fit never saw - is at most RULE_MARGIN x the error of the full float64 sum on the
+# same points in the same run.  4 x a few 1e-16, times the inverse log-Jacobian (condition 15 - 140 on physical tables), moves a
+# result by parts in 1e-14 to 1e-13: an order below the 1e-12 the results are held to (the every-pixel comparison with the exact
+# count stands at 2.6e-14, tests/test_gpu_gn_plane.py records margins >= 9.8e-13).  That product is also checked directly, point by
+# point (RULE_MAX_SHIFT), and the count grows until it holds too.
+RULE_VERSION = 1           # part of the key of the on-disk copy of a rule: bump with any change here
+RULE_MARGIN = 4.0
+RULE_MAX_AMPLIFICATION = 1.25      # sum |w_j| att_j / |sum w_j att_j| on every verification point: weights of both signs may not cancel
+RULE_MAX_SHIFT = 1.0e-13           # |B| err / max(|s|, 1) on every verification point, B the inverse log-Jacobian there: what the rule's error can
+                                   # move a result by, a tenth of the 1e-12 the results are held to.  The criterion alone compares two maxima,
+                                   # and the full sum's own is set by the rim of the table - exponents of several hundred at the unphysical
+                                   # ratios of the bundled 140 / 80 kV pair: 4.8e-14 - which would allow the same error in the middle of the
+                                   # plane, where the Jacobian turns it into 1e-12 of the result (measured: 90 nodes, 8.7e-13 on the device)
+RULE_MAX_SHARE = 0.75              # of the weighted energies: a longer rule is not worth a second table
+RULE_MIN_ENERGIES = 48             # the short cut's own limit (matdecomp.gn_device)
+RULE_FIT_POINTS = 12000
+RULE_VERIFY_POINTS = 20000
+RULE_MAX_UNUSABLE = 0.01           # share of verification points whose long-double reference is not finite and positive
+
+
+def one_step_cells(start):
+    """[n, n] bool: the cells of a start array that are open for the one-step acceptance (finite kappa and eps)."""
+    start = np.asarray(start)
+    n = int(start[3])
+    _, _, k0, k1 = start_layout(n)
+    if start[10] != 2.0 or start.size < k1:
+        return np.zeros((n, n), dtype=bool)
+    return np.all(np.isfinite(start[k0:k1].reshape(n, n, 2)), axis=2)
+
+
+def _rim(mask):
+    """The members of a 2-d mask with a 4-neighbour outside it (the array's own border counts as outside)."""
+    p = np.pad(mask, 1, mode='constant')
+    return mask & ~(p[:-2, 1:-1] & p[2:, 1:-1] & p[1:-1, :-2] & p[1:-1, 2:])
+
+
+def rule_fit_points(start, n_points=RULE_FIT_POINTS, thick_half_only=False):
+    """Where the rule is fitted [m, 2]: the tabulated fixed points at the corners of the one-step cells - every stride-th of
+    them in grid order (about ``n_points``) and ALL corners on the rim of the open region (its four borders: the thin and the
+    thick end, both rims of the ratio - negative second components included).  ``thick_half_only``: only the rows whose u0 is
+    above half of the largest open one - half of the range of attenuations, no thin ray (a deliberately wrong domain, for the
+    tests)."""
+    start = np.asarray(start, dtype=np.float64)
+    n = int(start[3])
+    cells = one_step_cells(start)
+    corners = np.zeros((n + 1, n + 1), dtype=bool)
+    for di in (0, 1):
+        for dj in (0, 1):
+            corners[di:n + di, dj:n + dj] |= cells
+    if thick_half_only:
+        rows = np.flatnonzero(corners.any(axis=1))
+        if rows.size:
+            corners[:max(int(np.ceil(rows[-1] - np.log(2.0) * start[5])), 0)] = False        # (row = (ln u0 - start[4]) start[5])
+    idx = np.flatnonzero(corners.ravel())
+    if idx.size == 0:
+        return np.zeros((0, 2))
+    keep = np.zeros(corners.size, dtype=bool)
+    keep[idx[::max(1, -(-idx.size // max(int(n_points), 1)))]] = True
+    keep |= _rim(corners).ravel()
+    return start[START_HEADER:START_HEADER + 2 * (n + 1) ** 2].reshape(-1, 2)[keep]
+
+
+def rule_verify_points(start, seed=0, n_points=RULE_VERIFY_POINTS):
+    """Where the rule is judged [m, 2] - no point of the fit: what the kernel starts a pixel from at the CENTRE of a one-step cell
+    (centre_interpolant), for ``n_points`` cells drawn with ``seed`` and every cell on the rim of the open region."""
+    start = np.asarray(start, dtype=np.float64)
+    n = int(start[3])
+    cells = one_step_cells(start)
+    rim = _rim(cells)
+    inner = np.flatnonzero((cells & ~rim).ravel())
+    rng = np.random.default_rng(seed)
+    pick = rng.choice(inner, size=min(int(n_points), inner.size), replace=False) if inner.size else inner
+    keep = rim.ravel().copy()
+    keep[pick] = True
+    return centre_interpolant(start, n).reshape(-1, 2)[keep]
+
+
+def _attenuation(mus, pts, dtype=np.float64):
+    """exp(clip(-(s . mu), +-700)) [n, nE] (the clip of matdecomp.py:116, as the kernel applies it)."""
+    mus, pts = np.asarray(mus, dtype=dtype), np.asarray(pts, dtype=dtype)
+    with np.errstate(all='ignore'):
+        return np.exp(np.clip(-(pts[:, 0, None] * mus[0][None, :] + pts[:, 1, None] * mus[1][None, :]), -700.0, 700.0))
+
+
+def rule_pivots(i0, mus, pts, normalise=True):
+    """(R, piv) of the column-pivoted QR of the stacked matrices of both measurements at the points pts [n, 2]; block k is K
+    diag(i0_k) with every row divided by nu_k (``normalise=False``: not divided - wrong on purpose, for the tests)."""
+    from scipy.linalg import qr
+    i0 = np.asarray(i0, dtype=np.float64)
+    K = _attenuation(mus, pts)
+    blocks = []
+    for k in (0, 1):
+        b = K * i0[k][None, :]
+        if normalise:
+            b = b / b.sum(axis=1, keepdims=True)
+        blocks.append(b)
+    A = np.vstack(blocks)
+    A = A[np.all(np.isfinite(A), axis=1)]
+    R, piv = qr(A, mode='r', pivoting=True, overwrite_a=True, check_finite=False)
+    return R, piv
+
+
+def rule_weights(R, piv, m, i0, identity=True):
+    """(nodes [m], w [2, m]) of the m-node rule of a pivoted QR: w_k = i0_k[J] * (X 1), X = [I, R11^-1 R12]
+    (``identity=False``: X without its identity part - wrong on purpose, for the tests)."""
+    from scipy.linalg import solve_triangular
+    i0 = np.asarray(i0, dtype=np.float64)
+    m = int(m)
+    c = solve_triangular(R[:m, :m], R[:m, m:].sum(axis=1), check_finite=False) if m < R.shape[1] else np.zeros(m)
+    if identity:
+        c = c + 1.0
+    J = np.asarray(piv[:m], dtype=np.int64)
+    return J, i0[:, J] * c[None, :]
+
+
+def rule_reference(i0, mus, pts):
+    """What a rule is judged against at the points pts [n, 2], as a dict: att [n, nE] (float64), ref [n, 2] = the sum of all
+    energies in long double, usable [n] (the reference is finite and positive), err_full [n, 2] = the relative error of the
+    full float64 sum, absB [n, p, k] = |B|, B the inverse of the model's log-Jacobian there (what the chord step multiplies a
+    relative error of nu_k with), size [n, 2] = max(|pts|, 1)."""
+    i0 = np.asarray(i0, dtype=np.float64)
+    mus = np.asarray(mus, dtype=np.float64)
+    att = _attenuation(mus, pts)
+    ref = _attenuation(mus, pts, np.longdouble) @ i0.astype(np.longdouble).T
+    with np.errstate(all='ignore'):
+        full = att @ i0.T
+        err_full = np.abs((full.astype(np.longdouble) - ref) / ref).astype(np.float64)
+        L = -np.stack([np.stack([att @ (i0[k] * mus[m]) for m in (0, 1)], axis=1) for k in (0, 1)], axis=1) / full[:, :, None]    # [n, k, m]
+        det = L[:, 0, 0] * L[:, 1, 1] - L[:, 0, 1] * L[:, 1, 0]
+        absB = np.abs(np.stack([np.stack([L[:, 1, 1], -L[:, 0, 1]], -1), np.stack([-L[:, 1, 0], L[:, 0, 0]], -1)], -2) / det[:, None, None])
+        usable = (np.all(np.isfinite(ref) & (ref > 0.0), axis=1) & np.all(np.isfinite(att), axis=1)
+                  & np.all(np.isfinite(absB), axis=(1, 2)))
+    return dict(att=att, ref=ref, usable=usable, err_full=err_full, absB=absB, size=np.maximum(np.abs(np.asarray(pts, dtype=np.float64)), 1.0))
+
+
+def rule_shift(v, err):
+    """The largest |B| err / max(|s|, 1) over the usable points and both components: how far relative errors err [n, 2] of the two
+    sums can move a chord step's result, in the units the results are held to."""
+    u = v['usable']
+    if not u.any():
+        return np.inf
+    with np.errstate(all='ignore'):
+        d = np.einsum('npk,nk->np', v['absB'][u], err[u]) / v['size'][u]
+    return float(np.where(np.isfinite(d), d, np.inf).max())
+
+
+def rule_errors(v, nodes, w):
+    """A rule on the points of ``v`` (rule_reference): (err [n, 2] = the relative error of its float64 sums against the
+    long-double reference, amp [n, 2] = sum |w_j| att_j / |sum w_j att_j|); inf where a value is not finite."""
+    w = np.asarray(w, dtype=np.float64)
+    a = v['att'][:, nodes]
+    with np.errstate(all='ignore'):
+        red = a @ w.T
+        err = np.abs((red.astype(np.longdouble) - v['ref']) / v['ref']).astype(np.float64)
+        amp = (a @ np.abs(w).T) / np.abs(red)
+    return np.where(np.isfinite(err), err, np.inf), np.where(np.isfinite(amp), amp, np.inf)
+
+
+def rule_meets(v, nodes, w):
+    """(ok, figures) of a rule on the points of ``v``: the criterion - its largest relative error at most RULE_MARGIN x the full
+    float64 sum's, measured on the same points - and the two conditions on every point: the weights do not cancel
+    (RULE_MAX_AMPLIFICATION), and the error cannot move a result by more than RULE_MAX_SHIFT of its size."""
+    u = v['usable']
+    err, amp = rule_errors(v, nodes, w)
+    fig = {'err_rule': float(err[u].max()) if u.any() else np.inf, 'err_full': float(v['err_full'][u].max()) if u.any() else np.inf,
+           'amplification': float(amp[u].max()) if u.any() else np.inf, 'shift_rule': rule_shift(v, err),
+           'shift_full': rule_shift(v, v['err_full'])}
+    ok = (fig['err_rule'] <= RULE_MARGIN * fig['err_full'] and fig['amplification'] <= RULE_MAX_AMPLIFICATION
+          and fig['shift_rule'] <= RULE_MAX_SHIFT)
+    return bool(ok), fig
+
+
+def residual_rule(start, i0, mus, stats=None, seed=0):
+    """The reduced residual rule of a pair of spectra over the domain of its gate table ``start`` (the host array of
+    assemble_start / validate_start; ``stats``: what its calibration saw of the pair, for pair_is_ill_posed): (rule, info) with
+    rule = {'nodes' [m] (indices into the energy axis of i0 / mus), 'w' [2, m]} or None, and info = what was measured (always a
+    dict: 'installed', 'reason' when not, 'nodes', 'n_energies', 'err_rule', 'err_full', 'amplification', 'shift_rule',
+    'shift_full', 'fit_points', 'verify_points', 'unusable_share', 'build_s').  Installed only if the one-step tables exist, the
+    pair is not ill-posed, the tables have at least RULE_MIN_ENERGIES weighted energies, the node count is at most RULE_MAX_SHARE
+    of them, the weights do not cancel (RULE_MAX_AMPLIFICATION) and the rule's error moves no result by more than RULE_MAX_SHIFT.
+    The node count is the smallest even one whose rule meets the criterion (RULE_MARGIN) and those two conditions on every
+    verification point (rule_meets)."""
+    import time
+    t0 = time.perf_counter()
+    info = {'installed': False, 'version': RULE_VERSION}
+
+    def no(reason):
+        info.update(reason=reason, build_s=time.perf_counter() - t0)
+        return None, info
+    i0 = np.asarray(i0, dtype=np.float64)
+    mus = np.asarray(mus, dtype=np.float64)
+    if i0.ndim == 3 and i0.shape[1] == 1:
+        i0 = i0[:, 0, :]
+    if i0.ndim != 2 or i0.shape[0] != 2 or mus.shape != (2, i0.shape[1]):
+        return no('tables')
+    used = np.flatnonzero(np.any(i0 > 0.0, axis=0))
+    info['n_energies'] = int(used.size)
+    if used.size < RULE_MIN_ENERGIES:
+        return no('fewer energies than the short cut takes')
+    if pair_is_ill_posed(stats):
+        return no('ill-posed pair')
+    if start is None or np.asarray(start).size < START_HEADER or np.asarray(start)[10] != 2.0:
+        return no('no one-step tables')
+    if np.finfo(np.longdouble).nmant < 63:
+        return no('no extended precision to verify against')
+    fit = rule_fit_points(start)
+    ver = rule_verify_points(start, seed)
+    fit = fit[np.all(np.isfinite(fit), axis=1)]
+    info.update(fit_points=int(len(fit)), verify_points=int(len(ver)))
+    if len(ver) < RULE_VERIFY_POINTS or len(fit) < 4 * used.size:
+        return no('too few open cells')
+    i0u, musu = i0[:, used], mus[:, used]
+    R, piv = rule_pivots(i0u, musu, fit)
+    v = rule_reference(i0u, musu, ver)
+    info['unusable_share'] = float(1.0 - v['usable'].mean())
+    if info['unusable_share'] > RULE_MAX_UNUSABLE:
+        return no('verification points without a reference')
+    m_max = min(int(RULE_MAX_SHARE * used.size), R.shape[0])
+    for m in range(2, m_max + 1, 2):
+        nodes, w = rule_weights(R, piv, m, i0u)
+        ok, fig = rule_meets(v, nodes, w)
+        if ok:
+            info.update(fig, nodes=int(m), negative_weights=int((w < 0.0).sum()), installed=True, build_s=time.perf_counter() - t0)
+            return {'nodes': used[nodes].astype(np.int64), 'w': np.ascontiguousarray(w)}, info
+    return no('no short rule meets the criterion and the conditions')
+
+
+def rule_cache_path(cache_dir, i0, mus, start):
+    """The rule's own file in the cache directory, keyed by the content of the tables (spectra, attenuations, gate table) and
+    RULE_VERSION; None without a directory."""
+    if cache_dir is None:
+        return None
+    import hashlib
+    import os
+    h = hashlib.sha256()
+    h.update(f'rule|{RULE_VERSION}|{GATE_VERSION}|{np.shape(i0)}'.encode())
+    for x in (i0, mus, start):
+        h.update(np.ascontiguousarray(x, dtype=np.float64).tobytes())
+    return os.path.join(cache_dir, f'rule_{h.hexdigest()[:32]}.bin')
+
+
+def rule_to_disk(path, rule, info):
+    """Keep (rule, info) of residual_rule (rule None: the verdict 'nothing installed' is kept as well): an .npz archive followed by
+    the sha256 of its bytes, so that no byte of the file can change unseen."""
+    if path is None:
+        return
+    try:
+        import hashlib
+        import io
+        import json
+        import os
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        nodes = np.zeros(0, dtype=np.int64) if rule is None else np.asarray(rule['nodes'], dtype=np.int64)
+        w = np.zeros((2, 0)) if rule is None else np.asarray(rule['w'], dtype=np.float64)
+        buf = io.BytesIO()
+        np.savez(buf, nodes=nodes, w=w, info=json.dumps(info, sort_keys=True))
+        body = buf.getvalue()
+        tmp = f'{path}.{os.getpid()}.tmp'
+        with open(tmp, 'wb') as f:
+            f.write(body + hashlib.sha256(body).digest())
+        os.replace(tmp, path)             # atomic: a reader sees the old file or the whole new one
+    except OSError:
+        pass                              # (a read-only home directory: the rule is simply not kept)
+
+
+def rule_from_disk(path, n_e):
+    """(rule, info) of an earlier process, or None: the file must be whole - its trailing checksum covers every byte before it - of
+    this RULE_VERSION, and fit tables of n_e energies."""
+    import os
+    if path is None or not os.path.exists(path):
+        return None
+    try:
+        import hashlib
+        import io
+        import json
+        with open(path, 'rb') as f:
+            raw = f.read()
+        body, digest = raw[:-32], raw[-32:]
+        if len(raw) <= 32 or hashlib.sha256(body).digest() != digest:
+            return None
+        with np.load(io.BytesIO(body), allow_pickle=False) as z:
+            nodes = np.ascontiguousarray(z['nodes'], dtype=np.int64)
+            w = np.ascontiguousarray(z['w'], dtype=np.float64)
+            info = json.loads(str(z['info']))
+        if info.get('version') != RULE_VERSION:
+            return None
+        if not info.get('installed'):
+            return (None, info) if nodes.size == 0 else None
+        if (nodes.size < 2 or w.shape != (2, nodes.size) or nodes.min() < 0 or nodes.max() >= n_e or len(set(nodes.tolist())) != nodes.size
+                or not np.all(np.isfinite(w)) or info.get('nodes') != nodes.size):
+            return None
+        return {'nodes': nodes, 'w': w}, info
+    except Exception:
+        return None

@@ -418,13 +418,19 @@ int dexct_download(void* host, const void* device_src, int64_t n_bytes, void* st
  *               (g / nu - 1) x second-derivative term (half the sums per energy); the term vanishes with the distance to a
  *               fixed point that reproduces its counts, what it leaves is second order and must be part of kappa
  *               (dex-ct-sim_amd/quadrature.py, newton_kappa(gauss_newton=True)).  All further steps are full Newton steps.
- *   blocks_per_cu   > 0: workgroups per CU of the queue kernels (0: what is resident; results do not depend on it). */
+ *               DEXCT_GN_FLAG_FULL_RESIDUAL (DEXCT_GN_FLAG_ONE_STEP launches): the chord step sums its residual over all energies
+ *               even when `start` carries a reduced residual rule (below).
+ *   blocks_per_cu   > 0: workgroups per CU of the queue kernels (0: what is resident; results do not depend on it).
+ * THE REDUCED RESIDUAL RULE (optional).  [10] = 3 instead of 2 says that, behind the power form of the interpolant ([11]: its
+ * offset o, 72 n^2 doubles long), the array carries a block made by dexct_gn_reduced_rows: the one-step launch then sums the
+ * residual of its chord step over the block's rows instead of the full tables.  A start array with [10] = 2 runs as before. */
 #define DEXCT_GN_DEFAULT_STOP_TOL 1e-12
 #define DEXCT_GN_PASS_COUNT 1
 #define DEXCT_GN_PASS_SHORTCUT 2
 #define DEXCT_GN_FLAG_FULL_LOOP 1
 #define DEXCT_GN_FLAG_NATURAL_ORDER 2
 #define DEXCT_GN_FLAG_ONE_STEP 4
+#define DEXCT_GN_FLAG_FULL_RESIDUAL 8
 typedef struct dexct_gn_options {
   double stop_tol;
   int32_t out_rows, out_channels;
@@ -474,7 +480,9 @@ typedef struct dexct_gn_options {
  * a number >= 0 is ignored); DEXCT_GN_FULL_LOOP=1 = DEXCT_GN_FLAG_FULL_LOOP on every call; DEXCT_GN_BLOCKS_PER_CU=<n> = the
  * default of options->blocks_per_cu; DEXCT_GN_COOP_BELOW=<pixels> moves the size below which the cooperative kernel runs;
  * DEXCT_GN_SORT=0 = DEXCT_GN_FLAG_NATURAL_ORDER on every call; DEXCT_GN_TILES_PER_FETCH=<n> queue positions a wave reserves per
- * atomic. */
+ * atomic; DEXCT_GN_REDUCED=0 = DEXCT_GN_FLAG_FULL_RESIDUAL on every call.  The uint64 at byte offset 104 of the workspace holds,
+ * after a DEXCT_GN_FLAG_ONE_STEP launch, the number of table rows the chord residual summed per pixel (n_energies: the full
+ * tables). */
 int64_t dexct_gn_workspace_bytes(int32_t n_energies, int32_t n_bins);
 int dexct_gn_decompose(const void* g1, const void* g2, int32_t g_is_f64, int64_t n_pix, const double* i0,
                        const double* mus, int32_t n_energies, int32_t n_bins, int32_t bin_div, int32_t n_iters,
@@ -488,6 +496,20 @@ int dexct_gn_decompose(const void* g1, const void* g2, int32_t g_is_f64, int64_t
  * mu[p][e] likewise.  i0 [2][n_energies], mus [2][n_energies] device float64 (one shared spectrum per measurement). */
 int dexct_gn_model_sums(const double* a, int64_t n_states, const double* i0, const double* mus, int32_t n_energies,
                         double* nu_out, double* g_out, double* s_out, void* stream);
+
+/* The device rows of a REDUCED RESIDUAL RULE (dex-ct-sim_amd/quadrature.py, residual_rule): n_nodes energies `nodes` of the
+ * tables, with new weights w0 / w1 (one per node and measurement; host arrays, like mus [2][n_energies]) under which
+ * sum_j w_k[j] exp(-(a0 mu0 + a1 mu1)[nodes[j]]) reproduces the expected counts nu_k(a) of ALL energies to rounding over the
+ * start values of the short cut.  Pure host code; `block` (host, block_len >= DEXCT_GN_REDUCED_HEADER + 14 n_nodes doubles)
+ * receives what the caller appends to the device copy of the start array: [0] rows kept (nodes without weight are dropped),
+ * [1..6] the sizes of the classes nA, nAc, nB, nBc, nC, nCc (both measurements weight the node / only 0 / only 1; of each, the
+ * first ..c always clip the exponent), [7], [8] the largest mu0 / mu1 of the clip-free rows, [9] doubles used, the rest of the
+ * header 0; then the rows in the format of the full tables - (-mu0 K, -mu1 K) with K = 2048 / ln 2 in the same arithmetic, so a
+ * kept energy has the exponent bits it has there, w0 in slot 2, w1 in slot 8, every other slot 0 - sorted into those classes
+ * (stable: the order of `nodes`).  DEXCT_EINVAL for a node outside the tables, a non-finite weight or a short block. */
+#define DEXCT_GN_REDUCED_HEADER 16
+int dexct_gn_reduced_rows(const double* mus, int32_t n_energies, const int32_t* nodes, int32_t n_nodes, const double* w0,
+                          const double* w1, double* block, int64_t block_len);
 
 /* Air mask of get_basismat_sinos (matdecomp.py:194-205): out_a[2p], out_a[2p+1] = 0 wherever
  * g1[p] >= thresh_value (thresh_value = mask_thresh * global max, computed by the caller so that a
