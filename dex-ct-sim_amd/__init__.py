@@ -6,10 +6,11 @@ Host code mirrors the reference's call surface; the work runs in ``libdexct_hip.
 (include/dexct.h) - importing the compute modules fails if that library is not built.
 """
 from .system import (FanBeamGeometry, Material, Phantom, ScannerGeometry, Spectrum, VoxelPhantom,  # noqa: F401
-                     read_parameter_file, xRaySpectrum)
+                     energy_bins, read_parameter_file, xRaySpectrum)
 
 __all__ = ['FanBeamGeometry', 'ScannerGeometry', 'VoxelPhantom', 'Phantom', 'xRaySpectrum', 'Spectrum', 'Material',
-           'read_parameter_file', 'get_sino', 'get_sinos', 'get_recon', 'get_basismat_sinos', 'do_matdecomp_gn']
+           'read_parameter_file', 'get_sino', 'get_sinos', 'get_recon', 'get_basismat_sinos', 'do_matdecomp_gn', 'energy_bins',
+           'get_basismat_sinos_multi', 'decomposition_tables_multi']
 
 
 def __getattr__(name):
@@ -23,7 +24,8 @@ def __getattr__(name):
     if name in ('make_vmi', 'measure_roi', 'vmi_roi_sweep', 'vmi_rmse_sweep'):
         from . import plots
         return getattr(plots, name)
-    if name in ('get_basismat_sinos', 'do_matdecomp_gn', 'optimize_sino', 'optimize_sino_cpu'):
+    if name in ('get_basismat_sinos', 'do_matdecomp_gn', 'optimize_sino', 'optimize_sino_cpu', 'get_basismat_sinos_multi',
+                'decomposition_tables_multi', 'gn_device_multi'):
         from . import matdecomp
         return getattr(matdecomp, name)
     raise AttributeError(name)

@@ -16,7 +16,8 @@ SYMBOLS = ['dexct_strerror', 'dexct_abi_version', 'dexct_last_hip_error', 'dexct
            'dexct_siddon_project_grouped_packed', 'dexct_poisson_detect', 'dexct_vmi', 'dexct_label_moments', 'dexct_fdk_backproject', 'dexct_sino_allgather', 'dexct_sino_gather', 'dexct_transpose_log', 'dexct_host_pin', 'dexct_host_touch', 'dexct_host_unpin', 'dexct_download',
            'dexct_volume_ids', 'dexct_volume_remap', 'dexct_fbp_parker', 'dexct_sino_log', 'dexct_cone_layout_groups', 'dexct_cone_project_grouped',
            'dexct_bhc_linearize', 'dexct_image_project', 'dexct_image_backproject', 'dexct_sirt_residual', 'dexct_sirt_update',
-           'dexct_gn_reduced_rows', 'dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes']
+           'dexct_gn_reduced_rows', 'dexct_gn_decompose_multi', 'dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes',
+           'dexct_gn_multi_workspace_bytes']
 
 
 class FanGeom(C.Structure):
@@ -65,6 +66,8 @@ GN_PASS_COUNT, GN_PASS_SHORTCUT = 1, 2
 GN_FLAG_FULL_LOOP, GN_FLAG_NATURAL_ORDER, GN_FLAG_ONE_STEP, GN_FLAG_FULL_RESIDUAL = 1, 2, 4, 8
 GN_REDUCED_HEADER = 16   # DEXCT_GN_REDUCED_HEADER
 GN_TABLE_ROW = 14        # doubles per energy row of the Newton tables (csrc/gn.hip, kTab)
+GN_MAX_MEAS, GN_MAX_MATS = 4, 3   # DEXCT_GN_MAX_MEAS, DEXCT_GN_MAX_MATS (dexct_gn_decompose_multi)
+GN_MULTI_FULL_LOOP = 1   # DEXCT_GN_MULTI_FULL_LOOP
 
 
 def gn_options(stop_tol=None, out_rows=0, out_channels=0, kernel=0, gn_pass=0, iterations=None, start=None, flags=0,
@@ -178,7 +181,10 @@ def load():
     lib.dexct_gn_model_sums.argtypes = [vp, i64, vp, vp, i32, vp, vp, vp, vp]
     lib.dexct_reduce_max.argtypes = [vp, i32, i64, vp, vp]
     lib.dexct_gn_reduced_rows.argtypes = [vp, i32, vp, i32, vp, vp, vp, i64]
-    for name in SYMBOLS[3:-2]:
+    lib.dexct_gn_decompose_multi.argtypes = [vp, i32, i64, i32, i32, vp, vp, i32, i32, vp, f64, i32, vp, vp, vp]
+    lib.dexct_gn_multi_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.dexct_gn_multi_workspace_bytes.restype = i64
+    for name in SYMBOLS[3:-3]:
         getattr(lib, name).restype = C.c_int
     _lib = lib
     return lib

@@ -7,6 +7,10 @@ Same public names and argument meaning as /root/reference/matdecomp.py:
 ``dexct_gn_decompose``; this module only builds the energy tables the way the reference does
 and moves arrays.  There is no NumPy or CuPy compute path here.
 
+Beyond the reference's two spectra and two materials: ``optimize_sino`` takes what the reference's routine takes - K = 2 .. 4
+measurements, M = 2 .. 3 <= K basis materials - and ``decomposition_tables_multi`` / ``get_basismat_sinos_multi`` build the
+tables and the masked sinograms for them (``dexct_gn_decompose_multi``, csrc/gn_multi.hip); K = M = 2 keeps its own path.
+
 Error behaviour: the reference raises ``numpy.linalg.LinAlgError`` when a pixel's 2x2 Hessian is
 exactly singular (matdecomp.py:125); the kernel never traps and leaves inf/NaN in such a pixel
 (masked air pixels are set to 0 afterwards exactly as in the reference, :204-205).
@@ -603,10 +607,21 @@ def optimize_sino(Sino_gg, ee, i0, mus, n_iters, verbose=True, dtype=None, preci
     slower per-lane-table kernel; the tiled spectrum do_matdecomp_gn builds, :151, takes the fast path) or
     [2, nEnergies]; mus [2, nEnergies].
     Returns Sino_aa [nViews, nBins, 2] float64 NumPy.  ``ee`` is unused, as in the reference.
+
+    The reference's routine is general in both leading dimensions, and so is this one: Sino_gg [K, nViews, nBins] with
+    K = 2 .. 4 measurements, mus [M, nEnergies] with M = 2 .. 3 <= K materials, i0 [K, nEnergies] or that spectrum tiled over the
+    channels, [K, nBins, nEnergies]; returns [nViews, nBins, M].  Anything but K = M = 2 runs gn_device_multi: the reference's
+    fixed iteration count in float64.  The keywords of the 2 x 2 path (``precision='mixed'``, ``stop_tol > 0``, ``two_level``,
+    ``audit``, the tuning knobs) raise ValueError there when set to something else than their default - they are never
+    silently ignored; ``full_loop`` is honoured.  Channel-dependent spectra exist for K = M = 2 only.
     """
     i0 = np.asarray(i0, dtype=np.float64)
     if i0.ndim == 3 and np.all(i0 == i0[:, :1, :]):
         i0 = i0[:, 0, :]                 # one spectrum tiled over the channels (:151): the fast path
+    if (int(np.shape(Sino_gg)[0]), int(np.shape(mus)[0])) != (2, 2):
+        # more than two measurements or a third basis material: the general kernel (gn_device_multi)
+        return _optimize_sino_multi(Sino_gg, i0, mus, n_iters, dict(precision=precision, stop_tol=stop_tol, two_level=two_level,
+                                                                    audit=audit, audit_strict=audit_strict, **gn_knobs))
     if i0.ndim == 3 and i0.shape[1] != np.asarray(Sino_gg).shape[2]:
         raise ValueError('i0 has a different number of bins than the sinogram')
     dev = device()
@@ -623,6 +638,108 @@ def optimize_sino(Sino_gg, ee, i0, mus, n_iters, verbose=True, dtype=None, preci
 
 
 optimize_sino_cpu = optimize_sino   # the reference's NumPy twin (:87); same engine here
+
+
+# ---- K = 2 .. 4 measurements, M = 2 .. 3 basis materials (csrc/gn_multi.hip, dexct_gn_decompose_multi) -----------------------
+# The general form of the reference's routine: three tube voltages, three or four photon-counting bins, a third basis with a
+# K-edge.  One kernel, the reference's fixed iteration count in float64; none of the 2 x 2 path's machinery (tolerance stop,
+# short cut, mixed precision, audit) exists here, and asking for it raises.
+GN_MAX_MEAS, GN_MAX_MATS = _native.GN_MAX_MEAS, _native.GN_MAX_MATS
+
+
+def _check_multi_shapes(n_meas, shp_i0, shp_mu, n_iters):
+    """(K, M, nE) of a call to the general kernel, or ValueError naming the limit.  No device access."""
+    shp_i0, shp_mu = tuple(shp_i0), tuple(shp_mu)
+    if len(shp_mu) != 2:
+        raise ValueError(f'mus must be [nMats, nEnergies], got shape {shp_mu}')
+    n_mats, n_e = int(shp_mu[0]), int(shp_mu[1])
+    if not 2 <= n_meas <= GN_MAX_MEAS:
+        raise ValueError(f'{n_meas} measurements: the decomposition takes 2 to {GN_MAX_MEAS} (what one traversal detects)')
+    if not 2 <= n_mats <= GN_MAX_MATS:
+        raise ValueError(f'{n_mats} basis materials: the decomposition takes 2 to {GN_MAX_MATS}')
+    if n_mats > n_meas:
+        raise ValueError(f'{n_mats} basis materials cannot be determined from {n_meas} measurements')
+    if len(shp_i0) == 3:
+        raise ValueError(f'channel-dependent spectra i0 [nMeas, nBins, nEnergies] are supported for 2 measurements and 2 basis '
+                         f'materials only (got {n_meas} and {n_mats}); pass one spectrum per measurement, [nMeas, nEnergies]')
+    if shp_i0 != (n_meas, n_e):
+        raise ValueError(f'i0 must be [{n_meas}, {n_e}] (one spectrum per measurement on the energies of mus), got shape {shp_i0}')
+    if not 1 <= n_e <= 4096:
+        raise ValueError(f'{n_e} energies: the decomposition takes 1 to 4096')
+    if int(n_iters) < 1:
+        raise ValueError(f'n_iters={n_iters!r} must be at least 1')
+    return n_meas, n_mats, n_e
+
+
+_MULTI_DEFAULTS = {
+    'precision': lambda v: v in (None, 'f64'),
+    'stop_tol': lambda v: v is None or (not isinstance(v, (bool, str)) and v == 0),
+    'two_level': lambda v: v is None or v is False,
+    'audit': lambda v: v is None or (not isinstance(v, (bool, str)) and v == 0),
+    'audit_strict': lambda v: v is None,
+    'kernel': lambda v: v == 0,
+    'natural_order': lambda v: not v,
+    'blocks_per_cu': lambda v: v == 0,
+    'reduced': lambda v: v is None,
+    'full_loop': lambda v: True,
+}
+
+
+def _reject_two_by_two_keywords(kw):
+    """The keywords that only exist for the 2 x 2 path must be at their defaults on the general path (``full_loop`` is shared)."""
+    for name, value in kw.items():
+        if name not in _MULTI_DEFAULTS or not _MULTI_DEFAULTS[name](value):
+            raise ValueError(f'{name}={value!r} exists for 2 measurements and 2 basis materials only: the general decomposition '
+                             f'runs the fixed iteration count in float64')
+
+
+def gn_device_multi(g, i0, mus, n_iters, mask_max=None, mask_frac=0.95, full_loop=False, out=None):
+    """The decomposition for K = 2 .. 4 measurements and M = 2 .. 3 <= K basis materials (dexct_gn_decompose_multi).
+    g: device tensor [K, ...] of counts (float32 or float64); i0 [K, nE], mus [M, nE]: host arrays or device tensors (float64
+    on the device).  ``mask_max``: device float64 scalar - pixels with g[0] >= mask_frac * max get 0 in every component and
+    are not iterated.  ``full_loop``: run every iteration (the default ends a pixel whose update returned its own input bit for
+    bit; the results are the same bits).  Returns a device tensor g.shape[1:] + (M,) float64: the state after n_iters
+    iterations of matdecomp.py:114-125."""
+    if not isinstance(g, torch.Tensor) or g.dim() < 2:
+        raise ValueError('g must be a device tensor [nMeas, ...]')
+    shp_i0 = tuple(i0.shape) if hasattr(i0, 'shape') else np.shape(i0)
+    if len(shp_i0) == 3 and shp_i0[1] == 1:
+        i0, shp_i0 = i0.reshape(shp_i0[0], shp_i0[2]), (shp_i0[0], shp_i0[2])
+    n_meas, n_mats, n_e = _check_multi_shapes(int(g.shape[0]), shp_i0, tuple(mus.shape) if hasattr(mus, 'shape') else np.shape(mus),
+                                              n_iters)
+    shape = tuple(g.shape[1:])
+    n_pix = int(np.prod(shape))
+    if out is not None and (out.numel() != n_mats * n_pix or out.dtype != torch.float64 or not out.is_contiguous()):
+        raise ValueError(f'out must be a contiguous float64 tensor with {n_mats} values per pixel')
+    lib = _native.load()
+    dev = g.device
+    if g.dtype not in (torch.float32, torch.float64):
+        g = g.to(torch.float64)
+    g = g.contiguous()
+    i0_d = to_dev(i0 if isinstance(i0, torch.Tensor) else np.asarray(i0, dtype=np.float64), torch.float64, dev)
+    mus_d = to_dev(mus if isinstance(mus, torch.Tensor) else np.asarray(mus, dtype=np.float64), torch.float64, dev)
+    a = out if out is not None else torch.empty(shape + (n_mats,), dtype=torch.float64, device=dev)
+    if n_pix == 0:
+        return a
+    ws = torch.empty(lib.dexct_gn_multi_workspace_bytes(n_meas, n_mats, n_e), dtype=torch.uint8, device=dev)
+    _native.check(lib.dexct_gn_decompose_multi(ptr(g), int(g.dtype == torch.float64), n_pix, n_meas, n_mats, ptr(i0_d), ptr(mus_d),
+                                               n_e, int(n_iters), ptr(mask_max), float(mask_frac),
+                                               _native.GN_MULTI_FULL_LOOP if full_loop else 0, ptr(a), ptr(ws), stream_ptr()),
+                  'dexct_gn_decompose_multi')
+    return a
+
+
+def _optimize_sino_multi(Sino_gg, i0, mus, n_iters, keywords):
+    """optimize_sino for anything but 2 measurements and 2 materials; i0 already collapsed where it was one tiled spectrum."""
+    shp_g = tuple(np.shape(Sino_gg))
+    if len(shp_g) != 3:
+        raise ValueError(f'Sino_gg must be [nMeas, nViews, nBins], got shape {shp_g}')
+    mus = np.asarray(mus, dtype=np.float64)
+    _check_multi_shapes(int(shp_g[0]), i0.shape, mus.shape, n_iters)
+    _reject_two_by_two_keywords(keywords)
+    dev = device()
+    g = _as_device_counts(np.asarray(Sino_gg), dev)
+    return to_host(gn_device_multi(g, i0, mus, n_iters, full_loop=bool(keywords.get('full_loop', False))))
 
 
 def decomposition_tables(ct, spec1, spec2):
@@ -821,3 +938,64 @@ def get_basismat_sinos(ct, sino_raw_1, sino_raw_2, spec1, spec2, n_iters=30, mas
         return a[..., 0], a[..., 1]
     a = to_host(a)          # page-locked: one DMA; the two results are views of this one buffer, like the reference's
     return a[..., 0], a[..., 1]
+
+
+def decomposition_tables_multi(ct, specs, materials=(matcomp1, matcomp2)):
+    """matdecomp.py:140-160 for any number of spectra and basis materials: (ee, i0 [K, nE], mus [M, nE]) - the union energy
+    grid of all spectra, dE with the first bin from 0, the detector response (times E for an energy-integrating detector),
+    np.interp of each spectrum, xcompy.mixatten of each material.  With two spectra and the default materials this is
+    decomposition_tables."""
+    specs = list(specs)
+    if not specs:
+        raise ValueError('at least one spectrum is needed')
+    ee = np.array(sorted(set(np.concatenate([np.asarray(sp.E, dtype=np.float64) for sp in specs]))))
+    dE = np.append([ee[0]], ee[1:] - ee[:-1])          # 1st energy bin is 0 to E[0]
+    detresponse = np.interp(ee, ct.det_E, ct.det_eta_E)
+    if ct.eid:
+        detresponse = detresponse * ee
+    i0 = np.stack([np.interp(ee, sp.E, sp.I0) * detresponse * dE for sp in specs])
+    mus = np.stack([xc.mixatten(m, ee) for m in materials])
+    return ee, i0, mus
+
+
+def get_basismat_sinos_multi(ct, sinos, specs, materials=(matcomp1, matcomp2), n_iters=30, mask_thresh=0.95, strict=False):
+    """get_basismat_sinos (matdecomp.py:167-207) for K = 2 .. 4 sinograms ``sinos`` of the spectra ``specs`` and M = 2 .. 3 <= K
+    basis ``materials`` (compositions as xcompy.mixatten takes them): air mask from sinos[0] (``>= mask_thresh * max``, as the
+    reference takes it from sino_raw_1), Newton decomposition with the fixed iteration count, masked pixels exactly 0.
+    Returns a tuple of M sinograms of sinos[0]'s shape, float64.  NumPy in -> NumPy out (views of one buffer); device tensors
+    in -> device tensors out.  ``strict=True`` raises SingularHessianError when a pixel outside the mask ends non-finite; the
+    default returns the inf / NaN in place.  Single process only."""
+    sinos, specs, materials = list(sinos), list(specs), list(materials)
+    if len(sinos) != len(specs):
+        raise ValueError(f'{len(sinos)} sinograms for {len(specs)} spectra')
+    shapes = {tuple(np.shape(s)) for s in sinos}
+    if len(shapes) != 1:
+        raise ValueError(f'the sinograms must agree in shape, got {sorted(shapes)}')
+    n_meas, n_mats = len(sinos), len(materials)
+    if not 2 <= n_meas <= GN_MAX_MEAS:
+        raise ValueError(f'{n_meas} measurements: the decomposition takes 2 to {GN_MAX_MEAS} (what one traversal detects)')
+    if not 2 <= n_mats <= min(GN_MAX_MATS, n_meas):
+        raise ValueError(f'{n_mats} basis materials: the decomposition takes 2 to {GN_MAX_MATS}, and no more than measurements')
+    if int(n_iters) < 1:
+        raise ValueError(f'n_iters={n_iters!r} must be at least 1')
+    if _shard.world()[1] > 1:
+        raise NotImplementedError('get_basismat_sinos_multi runs on a single process; shard the views by hand under torch.distributed')
+    _, i0, mus = decomposition_tables_multi(ct, specs, materials)
+    lib = _native.load()
+    dev = device()
+    tensors_in = isinstance(sinos[0], torch.Tensor)
+    first = _as_device_counts(sinos[0], dev)
+    g = torch.stack([first] + [_as_device_counts(s, dev).to(first.dtype) for s in sinos[1:]])
+    gmax = torch.empty((), dtype=torch.float64, device=dev)
+    _native.check(lib.dexct_reduce_max(ptr(g[0]), int(g.dtype == torch.float64), g[0].numel(), ptr(gmax), stream_ptr()), 'dexct_reduce_max')
+    a = gn_device_multi(g, i0, mus, n_iters, mask_max=gmax, mask_frac=float(mask_thresh))
+    if strict:
+        bad = ~torch.isfinite(a).all(dim=-1)          # masked pixels are exactly 0, hence finite
+        n_bad = int(bad.sum().item())
+        if n_bad:
+            first_bad = bad.flatten().nonzero()[:1].flatten().tolist()
+            raise SingularHessianError(f'Singular matrix: {n_bad} pixel(s) outside the air mask ended non-finite '
+                                       f'after {n_iters} Newton iterations (first flat index: {first_bad})')
+    if not tensors_in:
+        a = to_host(a)
+    return tuple(a[..., m] for m in range(n_mats))

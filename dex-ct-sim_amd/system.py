@@ -216,6 +216,21 @@ class xRaySpectrum:
         return np.concatenate([[self.E[0]], np.diff(self.E)])
 
 
+def energy_bins(spec, edges):
+    """The threshold bins of a photon-counting detector as spectra: window j is ``spec`` with I0 zeroed outside
+    [edges[j], edges[j+1]) - same energies, so get_sinos scans all windows in one traversal and
+    matdecomp.get_basismat_sinos_multi decomposes them.  Inside [edges[0], edges[-1]) the windows sum to ``spec``."""
+    edges = np.asarray(edges, dtype=np.float64)
+    if edges.ndim != 1 or edges.size < 2 or not np.all(np.diff(edges) > 0.0):
+        raise ValueError('edges must be at least two increasing energies [keV]')
+    E = np.asarray(spec.E, dtype=np.float64)
+    out = []
+    for j in range(edges.size - 1):
+        inside = (E >= edges[j]) & (E < edges[j + 1])
+        out.append(xRaySpectrum.from_arrays(f'{spec.name}[{edges[j]:g},{edges[j + 1]:g})', E.copy(), np.where(inside, spec.I0, 0.0)))
+    return out
+
+
 # README.md:14-16 spellings
 ScannerGeometry = FanBeamGeometry
 Phantom = VoxelPhantom

@@ -489,6 +489,40 @@ int dexct_gn_decompose(const void* g1, const void* g2, int32_t g_is_f64, int64_t
                        int32_t precision, int32_t n_polish, const double* mask_max, double mask_frac, double* out_a,
                        const dexct_gn_options* options, void* workspace, void* stream);
 
+/* The same decomposition for n_meas = 2 .. 4 measurements and n_mats = 2 .. 3 basis materials: the general form of
+ * optimize_sino_cpu (matdecomp.py:87-127 sums over nMeas and inverts an nMats x nMats Hessian) - three tube voltages, three or
+ * four photon-counting bins, a third basis with a K-edge.  Additive to ABI 6; dexct_gn_decompose is unchanged.
+ *   g[k*n_pix + p]          measured counts, [n_meas][n_pix] contiguous; g_is_f64 selects float64 (1) or float32 (0);
+ *                           aligned to its element size
+ *   i0[k*n_energies + e]    effective spectra (float64): one shared spectrum per measurement
+ *   mus[m*n_energies + e]   basis mass attenuation (float64)
+ *   out_a[n_mats*p + m]     density line integrals (float64), 8-byte aligned; every pixel's n_mats values are written
+ *   2 <= n_mats <= n_meas <= DEXCT_GN_MAX_MEAS, n_mats <= DEXCT_GN_MAX_MATS, 1 <= n_iters, 1 <= n_energies <= 4096, n_pix >= 0
+ *                           (0: nothing is launched); DEXCT_EINVAL / DEXCT_ERANGE before the first launch otherwise
+ *   mask_max, mask_frac     as above: a pixel whose measurement-0 count is >= mask_frac * *mask_max gets 0 in every component
+ *                           and is not iterated; NULL = no mask
+ *   flags                   0 or DEXCT_GN_MULTI_FULL_LOOP
+ *   workspace               device scratch of dexct_gn_multi_workspace_bytes(n_meas, n_mats, n_energies) bytes (0 for sizes
+ *                           outside the limits), 8-byte aligned: the per-energy rows the kernel reads through the scalar cache
+ *                           - the scaled -mu_m, then per measurement i0_k, i0_k mu_m, i0_k (mu_m mu_n), rounded as the
+ *                           reference's ssff / ssff2 (:102, :105); energies no measurement weights are left out (their terms
+ *                           are exact zeros).  Written by the call before it is read; no hidden state
+ * The mathematics is matdecomp.py:114-125 in float64: every component starts at 1e-6; atten = exp(clip(-sum_m a_m mu_m, +-700));
+ * nu, its gradient and Hessian; the Poisson gradient and the full Newton Hessian with the (g/nu - 1) second-derivative term;
+ * a -= H^-1 dF by the closed-form symmetric solve.  The call returns the state after n_iters iterations.  The only early exit is
+ * the one that cannot change that state - an update that returns its own input bit for bit in every component - and
+ * DEXCT_GN_MULTI_FULL_LOOP disables even that (the check that the exit changes no bit).  No tolerance stop, no short cut, no
+ * mixed precision, no environment variable.  A singular or non-finite Hessian leaves what IEEE arithmetic gives (inf / NaN) in
+ * that pixel only. */
+#define DEXCT_GN_MAX_MEAS 4     /* = DEXCT_MAX_SPECTRA: what one traversal can detect */
+#define DEXCT_GN_MAX_MATS 3
+#define DEXCT_GN_MULTI_FULL_LOOP 1
+int64_t dexct_gn_multi_workspace_bytes(int32_t n_meas, int32_t n_mats, int32_t n_energies);
+int dexct_gn_decompose_multi(const void* g, int32_t g_is_f64, int64_t n_pix, int32_t n_meas, int32_t n_mats,
+                             const double* i0, const double* mus, int32_t n_energies, int32_t n_iters,
+                             const double* mask_max, double mask_frac, int32_t flags, double* out_a,
+                             void* workspace, void* stream);
+
 /* The energy sums of the decomposition's forward model (matdecomp.py:116-121) at n_states states a [n][2] (device float64), for the
  * table assembly of the short cut (quadrature.py, assemble_start / validate_start; no counterpart in the reference): nu_out
  * [n][2] = sum_e i0[k][e] exp(clip(-(a0 mu0[e] + a1 mu1[e]), +-700)); g_out [n][2][2] = sum_e i0[k][e] mu[m][e] x the same
