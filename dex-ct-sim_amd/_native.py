@@ -65,6 +65,8 @@ class GnOptions(C.Structure):
 GN_PASS_COUNT, GN_PASS_SHORTCUT = 1, 2
 GN_FLAG_FULL_LOOP, GN_FLAG_NATURAL_ORDER, GN_FLAG_ONE_STEP, GN_FLAG_FULL_RESIDUAL = 1, 2, 4, 8
 GN_REDUCED_HEADER = 16   # DEXCT_GN_REDUCED_HEADER
+GN_WS_EXECUTED, GN_WS_PROGRESS, GN_WS_QUEUE_HEAD, GN_WS_STALLS, GN_WS_RESIDUAL_ROWS = 72, 80, 88, 96, 104   # DEXCT_GN_WS_*: byte offsets
+GN_WS_WORDS = slice(GN_WS_EXECUTED, GN_WS_RESIDUAL_ROWS + 8)   # ... of the workspace's diagnostic uint64 words; the span of all five
 GN_TABLE_ROW = 14        # doubles per energy row of the Newton tables (csrc/gn.hip, kTab)
 GN_MAX_MEAS, GN_MAX_MATS = 4, 3   # DEXCT_GN_MAX_MEAS, DEXCT_GN_MAX_MATS (dexct_gn_decompose_multi)
 GN_MULTI_FULL_LOOP = 1   # DEXCT_GN_MULTI_FULL_LOOP

@@ -149,6 +149,9 @@ __device__ __forceinline__ void energy_sums_f64(const double* __restrict__ tab, 
 // scaled tables)]: for the second part the clip of matdecomp.py:116 is the identity and is skipped (two FP64
 // instructions per energy), bit for bit the same result.
 struct EnergyClasses { int nA, nAc, nB, nBc, nC, nCc; double m0_free, m1_free; };
+__device__ __forceinline__ EnergyClasses gn_energy_classes(const double* __restrict__ ws) {      // from the workspace header
+  return EnergyClasses{(int)ws[1], (int)ws[4], (int)ws[2], (int)ws[5], (int)ws[3], (int)ws[6], ws[7], ws[8]};
+}
 
 // The 12 sums over energy a Newton step needs.  NPARTS = 1: all energies (the one-lane-per-pixel kernels).  NPARTS > 1:
 // share `part` of them - every class range is cut into NPARTS contiguous pieces - for the cooperative kernel, whose waves
@@ -291,7 +294,7 @@ __device__ __forceinline__ void newton_step_f32(const float* __restrict__ tab, E
 
 // Workspace layout (doubles): [0] = scale of the float32 tables, [1..3] = nA, nB, nC (energy classes), [4..6] =
 // how many of each class come first and always need the clip, [7..8] = max mu0 / mu1 over the clip-free parts,
-// [9] = (uint64, diagnostic) pixel-iterations the last gn_refill_kernel launch on this workspace executed,
+// [9] = (uint64, diagnostic; kWsExecuted ..) pixel-iterations the last gn_refill_kernel launch on this workspace executed,
 // [10] = (uint64, progress) pixels that launch has handed to its waves so far (added tile by tile while it runs),
 // [11] = (uint64) head of the tile queue, [12] = (uint64, diagnostic) lane-steps spent without a pixel because all of a
 // wave's result slots were waiting for stragglers,
@@ -299,6 +302,12 @@ __device__ __forceinline__ void newton_step_f32(const float* __restrict__ tab, E
 // tile-order region of gn_tile_* below: kSortBuckets ints (histogram), kMaxSortTiles ints (the order), kMaxSortTiles
 // uint16 (keys).
 constexpr int kWsHeader = 16;
+// the uint64 words [9] .. [13] by name (include/dexct.h publishes their byte offsets); the queue kernels get ONE pointer, to the
+// first of them (`counters`), and reach the others through gn_counter
+enum GnWsWord { kWsExecuted = DEXCT_GN_WS_EXECUTED / 8, kWsProgress = DEXCT_GN_WS_PROGRESS / 8, kWsQueueHead = DEXCT_GN_WS_QUEUE_HEAD / 8,
+                kWsStalls = DEXCT_GN_WS_STALLS / 8, kWsResidualRows = DEXCT_GN_WS_RESIDUAL_ROWS / 8 };
+static_assert(kWsExecuted == 9 && kWsResidualRows < kWsHeader, "the diagnostic words follow the energy classes inside the header");
+__device__ __forceinline__ unsigned long long* gn_counter(unsigned long long* counters, GnWsWord word) { return counters + (word - kWsExecuted); }
 constexpr int kSortBuckets = 2048;         // sign + exponent + 2 mantissa bits of a positive float32
 constexpr int kMaxSortTiles = 32768;       // 2.1e6 pixels: beyond that the order of the hand-out does not matter (profiles/r04_gn.md)
 
@@ -367,10 +376,10 @@ __global__ __launch_bounds__(256) void gn_tables_kernel(const double* __restrict
       ws[6] = (double)s_nc[2];
       ws[7] = m0f;
       ws[8] = m1f;
-      reinterpret_cast<unsigned long long*>(ws)[9] = 0ull;      // executed pixel-iterations, counted by gn_refill_kernel
-      reinterpret_cast<unsigned long long*>(ws)[10] = 0ull;     // finished pixels (progress of the running launch)
-      reinterpret_cast<unsigned long long*>(ws)[11] = 0ull;     // head of the tile queue of gn_refill_kernel
-      reinterpret_cast<unsigned long long*>(ws)[12] = 0ull;     // lane-steps stalled on result slots
+      reinterpret_cast<unsigned long long*>(ws)[kWsExecuted] = 0ull;      // executed pixel-iterations, counted by gn_refill_kernel
+      reinterpret_cast<unsigned long long*>(ws)[kWsProgress] = 0ull;      // finished pixels (progress of the running launch)
+      reinterpret_cast<unsigned long long*>(ws)[kWsQueueHead] = 0ull;     // head of the tile queue of gn_refill_kernel
+      reinterpret_cast<unsigned long long*>(ws)[kWsStalls] = 0ull;        // lane-steps stalled on result slots
     }
   }
   if (bin == 0) {                       // the histogram of the tile sort starts at zero
@@ -443,6 +452,13 @@ struct GnTiling {
   unsigned mul_r, sh_r, mul_c, sh_c; // n / tiles_r and n / tiles_c as (mulhi(n, mul) + n) >> sh (gn_magic): a tile is decoded per 64
                                      // pixels, and on the short cut - one step per pixel - two 30-instruction divisions showed
 };
+
+// The flag word dexct_gn_decompose hands its kernels (gn_kernel takes the first and third bit as its `exact_exit`)
+constexpr int kFlagExactExit = 1;     // end a pixel at the first state that repeats bit for bit
+constexpr int kFlagSorted = 2;        // the queue hands out gn_tile_order's tiles (thick tiles first)
+constexpr int kFlagConfirm = 4;       // the tolerance rule asks for two contracting steps (gn_converged)
+constexpr int kFlagReduced = 8;       // gn_shortcut_kernel<1>: use the reduced residual rule if the start array has one
+constexpr int kFlagFetchShift = 8, kFlagFetchMask = 0xFFF;      // bits 8..19: tiles per queue reservation
 
 // Division of a 32-bit n by an invariant d >= 1 (Granlund & Montgomery, the round-up form): s = ceil(log2 d),
 // m = floor(2^32 (2^s - d) / d) + 1, n / d = (mulhi(n, m) + n) >> s, the sum in 64 bits.  Exact for every n < 2^32.
@@ -548,7 +564,7 @@ __global__ __launch_bounds__(kGnBlock) void gn_kernel(const void* __restrict__ g
   for (int j = threadIdx.x; j < kPowN; j += kGnBlock) lds_pow[j] = pow_entry(j);
   __syncthreads();
   const float* __restrict__ tab32 = reinterpret_cast<const float*>(ws + kWsHeader + (size_t)n_bins * n_e * kTab);
-  const EnergyClasses ec{(int)ws[1], (int)ws[4], (int)ws[2], (int)ws[5], (int)ws[3], (int)ws[6], ws[7], ws[8]};
+  const EnergyClasses ec = gn_energy_classes(ws);
   const int64_t p = (int64_t)blockIdx.x * kGnBlock + threadIdx.x;
   if (p >= n_pix) return;
   const double* __restrict__ tab = ws + kWsHeader;
@@ -634,7 +650,7 @@ __global__ __launch_bounds__(kGnBlock) void gn_kernel(const void* __restrict__ g
   for (; it < n_iters; ++it) {
     double n0 = a0, n1 = a1;
     newton_step_f64(tab, lds_pow, ec, gd0, gd1, n0, n1);
-    if (exact_exit & 1) {
+    if (exact_exit & kFlagExactExit) {
       const long long b0 = __double_as_longlong(n0), b1 = __double_as_longlong(n1);
       if (b0 == __double_as_longlong(a0) && b1 == __double_as_longlong(a1)) hit = -1;
 #pragma unroll
@@ -642,7 +658,7 @@ __global__ __launch_bounds__(kGnBlock) void gn_kernel(const void* __restrict__ g
         if (k < it && b0 == h0[k] && b1 == h1[k] && hit != -1) hit = k;
       if (hit != -2) break;
       // the tolerance stop (float64 loop only; see gn_converged)
-      if (gn_converged(stop_tol, a0, a1, n0, n1, __longlong_as_double(h0[0]), __longlong_as_double(h1[0]), it, (exact_exit & 4) != 0,
+      if (gn_converged(stop_tol, a0, a1, n0, n1, __longlong_as_double(h0[0]), __longlong_as_double(h1[0]), it, (exact_exit & kFlagConfirm) != 0,
                        __longlong_as_double(h0[1]), __longlong_as_double(h1[1]))) {
         a0 = n0;
         a1 = n1;
@@ -668,8 +684,14 @@ __global__ __launch_bounds__(kGnBlock) void gn_kernel(const void* __restrict__ g
 }
 
 
-__device__ __forceinline__ const int* gn_tile_order(const unsigned long long* counters, int n_e) {      // counters = workspace word 9; shared-spectrum kernels: n_bins = 1
-  return reinterpret_cast<const int*>(reinterpret_cast<const char*>(counters - 9) + gn_ws_tables_bytes(n_e, 1)) + kSortBuckets;
+__device__ __forceinline__ long long gn_uniform(long long t) {      // lane 0's value, in scalar registers
+  return ((long long)__builtin_amdgcn_readfirstlane((int)(t >> 32)) << 32) | (long long)(unsigned)__builtin_amdgcn_readfirstlane((int)t);
+}
+__device__ __forceinline__ int gn_batch(int flags) {         // tiles per queue reservation, at least 1
+  return ((flags >> kFlagFetchShift) & kFlagFetchMask) > 0 ? ((flags >> kFlagFetchShift) & kFlagFetchMask) : 1;
+}
+__device__ __forceinline__ const int* gn_tile_order(const unsigned long long* counters, int n_e) {      // counters = workspace word kWsExecuted; shared-spectrum kernels: n_bins = 1
+  return reinterpret_cast<const int*>(reinterpret_cast<const char*>(counters - kWsExecuted) + gn_ws_tables_bytes(n_e, 1)) + kSortBuckets;
 }
 
 // ---- order of the hand-out for SMALL sinograms: longest tiles first ---------------------------------------------------
@@ -871,6 +893,7 @@ __device__ __forceinline__ bool gn_exit_or_advance(double n0, double n1, int n_i
 // ratios), kappa |a| is 100 on average, eps 2e-8 at the median point (2e-7 / 1e-5 at the 90th / 99th percentile: it shrinks and
 // grows with d1): ~99 % of the plane passes with orders to spare, the rest takes full Newton steps.
 constexpr int kStartHeader = 12;
+constexpr int kPowerCell = 6 * 6 * 2;  // doubles per cell of the power form: 6 x 6 coefficient pairs (quadrature.POWER_CELL)
 // THE REDUCED RESIDUAL RULE (round 8; include/dexct.h, dexct_gn_reduced_rows; quadrature.residual_rule).  The chord step needs nu_k
 // at start values that all lie on the surface the table tabulates, and over that surface the columns exp(-a . mu(e)) of the
 // energies are numerically dependent: a subset of the energies with new weights reproduces both sums to rounding.  Where the host
@@ -879,7 +902,6 @@ constexpr int kStartHeader = 12;
 // in slots 2 and 8); gn_shortcut_kernel<1> hands chord_residuals_f64 those rows instead of the workspace's.  Everything else
 // (the drain's Newton steps, STEPS == 2, the other kernels) sums over the full tables.
 constexpr int kRedHeader = 16;
-constexpr int kFlagReduced = 8;       // kernel flag of gn_shortcut_kernel<1>: use the block if the start array has one
 #ifndef DEXCT_GN_INTERP_UNROLL
 #define DEXCT_GN_INTERP_UNROLL 2      // rows of the 6 x 6 interpolation per loop trip (A/B: tools/probes/build_variant.sh)
 #endif
@@ -952,7 +974,7 @@ __device__ __forceinline__ bool gn_start(const double* __restrict__ start, const
     // derivative carried along, then along wx: 136 FMAs and no weights, against the Lagrange form's 180 FMAs and ~90
     // instructions of weights.  It is the same polynomial: s and B agree with the Lagrange form to rounding
     // (tests/test_gn_power_form.py).
-    const d2* __restrict__ coef = reinterpret_cast<const d2*>(start + (int)start[11]) + (size_t)(i * n + j) * 36;
+    const d2* __restrict__ coef = reinterpret_cast<const d2*>(start + (int)start[11]) + (size_t)(i * n + j) * (kPowerCell / 2);
     // one row a: p = sum_b C_ab wy^b and d = its derivative along wy, by Horner (the first step of each peeled)
     auto row = [&](int a, d2& p, d2& d) {
       const d2* __restrict__ r = coef + 6 * a;
@@ -1049,21 +1071,20 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_refill_kernel(const void* __re
                                                              int g_is_f64, long long n_pix, const double* __restrict__ ws,
                                                              int n_e, int n_iters, GnTiling tl,
                                                              const double* __restrict__ mask_max, double mask_frac,
-                                                             int flags, double stop_tol,      // flags: bit 0 exact repeated-state exit, bit 1 sorted hand-out, bit 2 the rule asks for two contracting steps, bits 8..19: tiles per queue reservation
+                                                             int flags, double stop_tol,      // flags: kFlag*
                                                              double* __restrict__ out_a,
                                                              unsigned long long* __restrict__ counters,
                                                              unsigned char* __restrict__ iters) {
   typedef double d2 __attribute__((ext_vector_type(2)));
-  // `counters` = the workspace words 9.. (executed, progress, queue head, stalls): ONE pointer, and the tile order is found
+  // `counters` = the workspace words kWsExecuted.. (executed, progress, queue head, stalls): ONE pointer, and the tile order is found
   // from it too (the table pointer `ws` stays read-only for the compiler: its loads are scalar loads)
-  auto counter = [&](int k) { return counters + (k - 9); };
   __shared__ double lds_pow[kPowN];                                      // 16 KB
   __shared__ d2 lds_out[kGnBlock / kWave][kSlots * kTilePix];            // 12 KB: with the table 28 KB = 5 workgroups per CU
   __shared__ unsigned char lds_it[COUNT ? kGnBlock / kWave : 1][COUNT ? kSlots * kTilePix : 1];
   unsigned char* __restrict__ my_it = lds_it[COUNT ? (threadIdx.x >> 6) : 0];
   for (int j = threadIdx.x; j < kPowN; j += kGnBlock) lds_pow[j] = pow_entry(j);
   __syncthreads();                        // the only barrier: waves leave the loop below independently
-  const EnergyClasses ec{(int)ws[1], (int)ws[4], (int)ws[2], (int)ws[5], (int)ws[3], (int)ws[6], ws[7], ws[8]};
+  const EnergyClasses ec = gn_energy_classes(ws);
   const double* __restrict__ tab = ws + kWsHeader;
   d2* __restrict__ my_out = lds_out[threadIdx.x >> 6];
   const int lane = threadIdx.x & 63;
@@ -1081,7 +1102,7 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_refill_kernel(const void* __re
   GnTile ct{0, 0, 0, 0};                  // the tile being handed out
   bool exhausted = false;
   unsigned n_exec = 0, n_stall = 0;       // Newton steps executed; lane-steps spent waiting for a free slot (diagnostic)
-  const int batch = ((flags >> 8) & 0xFFF) > 0 ? ((flags >> 8) & 0xFFF) : 1;      // queue positions reserved per atomic (flags bits 8..19)
+  const int batch = gn_batch(flags);      // queue positions reserved per atomic
   int q_next = 0, q_end = 0;              // the reserved positions not yet handed out (n_tiles < 2^31)
   unsigned handed = 0u;                   // pixels of the tiles handed out since the last reservation (progress word)
 
@@ -1137,18 +1158,17 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_refill_kernel(const void* __re
           // word (the pixels of the tiles handed out since the last reservation)
           long long t = 0;
           if (lane == 0) {
-            t = (long long)atomicAdd(counter(11), (unsigned long long)batch);
-            if (handed) atomicAdd(counter(10), (unsigned long long)handed);        // progress: handed to a wave
+            t = (long long)atomicAdd(gn_counter(counters, kWsQueueHead), (unsigned long long)batch);
+            if (handed) atomicAdd(gn_counter(counters, kWsProgress), (unsigned long long)handed);        // progress: handed to a wave
           }
           handed = 0u;
-          t = ((long long)__builtin_amdgcn_readfirstlane((int)(t >> 32)) << 32) |
-              (long long)(unsigned)__builtin_amdgcn_readfirstlane((int)t);
+          t = gn_uniform(t);
           if (t >= tl.n_tiles) { exhausted = true; break; }
           q_next = (int)t;
           q_end = t + batch < tl.n_tiles ? (int)t + batch : (int)tl.n_tiles;
         }
         long long t = q_next++;
-        if (flags & 2) t = gn_tile_order(counters, n_e)[t];     // queue position -> tile (thick tiles first, see gn_tile_key_kernel)
+        if (flags & kFlagSorted) t = gn_tile_order(counters, n_e)[t];     // queue position -> tile (thick tiles first, see gn_tile_key_kernel)
         ct = gn_decode_tile(tl, n_pix, t);
         const int n_valid = ct.nr * ct.nc;
 #pragma unroll
@@ -1199,8 +1219,8 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_refill_kernel(const void* __re
     // k + 2 states) determines every later iterate.  Written with selects instead of branches; idle lanes run
     // through it too and are ignored.
     bool by_rule = false;
-    const bool advance = gn_exit_or_advance(n0, n1, n_iters, flags & 1, stop_tol, a0, a1, it, h0, h1,
-                                            COUNT ? &by_rule : nullptr, (flags & 4) != 0);
+    const bool advance = gn_exit_or_advance(n0, n1, n_iters, flags & kFlagExactExit, stop_tol, a0, a1, it, h0, h1,
+                                            COUNT ? &by_rule : nullptr, (flags & kFlagConfirm) != 0);
     const bool fin = ent >= 0 && (!advance || it >= n_iters);
     const unsigned long long fb = __ballot(fin);
     if (fb != 0ull) {
@@ -1212,9 +1232,9 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_refill_kernel(const void* __re
     }
   }
   if (lane == 0) {
-    atomicAdd(counter(9), (unsigned long long)n_exec);            // one atomic per wave
-    if (n_stall) atomicAdd(counter(12), (unsigned long long)n_stall);
-    if (handed) atomicAdd(counter(10), (unsigned long long)handed);
+    atomicAdd(gn_counter(counters, kWsExecuted), (unsigned long long)n_exec);            // one atomic per wave
+    if (n_stall) atomicAdd(gn_counter(counters, kWsStalls), (unsigned long long)n_stall);
+    if (handed) atomicAdd(gn_counter(counters, kWsProgress), (unsigned long long)handed);
   }
 }
 
@@ -1247,7 +1267,6 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_shortcut_kernel(const void* __
                                                                unsigned long long* __restrict__ counters,
                                                                const double* __restrict__ start) {
   typedef double d2 __attribute__((ext_vector_type(2)));
-  auto counter = [&](int k) { return counters + (k - 9); };
   __shared__ double lds_pow[kPowN];                                      // 16 KB
   __shared__ d2 lds_out[kGnBlock / kWave][kTilePix];                     // 4 KB: one tile of results per wave
   __shared__ long long lds_snp[kGnBlock / kWave][kStashCap];             // 3 KB: the stash - input index of the pixel | kind,
@@ -1256,7 +1275,7 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_shortcut_kernel(const void* __
   __shared__ double lds_srad[kGnBlock / kWave][kStashCap];               // 3 KB: its acceptance radius  (38 KB: 4 workgroups per CU)
   for (int j = threadIdx.x; j < kPowN; j += kGnBlock) lds_pow[j] = pow_entry(j);
   __syncthreads();                        // the only barrier: waves work independently from here on
-  const EnergyClasses ec{(int)ws[1], (int)ws[4], (int)ws[2], (int)ws[5], (int)ws[3], (int)ws[6], ws[7], ws[8]};
+  const EnergyClasses ec = gn_energy_classes(ws);
   const double* __restrict__ tab = ws + kWsHeader;
   // the rows the chord residual sums over: the reduced rule's if the start array carries one (wave-uniform, read once)
   const double* __restrict__ res_tab = tab;
@@ -1265,12 +1284,12 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_shortcut_kernel(const void* __
     int res_rows = n_e;
     if ((flags & kFlagReduced) != 0 && start[10] == 3.0) {
       const int nc = (int)start[3];
-      const double* __restrict__ blk = start + ((int)start[11] + 72 * nc * nc);
+      const double* __restrict__ blk = start + ((int)start[11] + kPowerCell * nc * nc);
       res_rows = (int)blk[0];
       res_ec = EnergyClasses{(int)blk[1], (int)blk[2], (int)blk[3], (int)blk[4], (int)blk[5], (int)blk[6], blk[7], blk[8]};
       res_tab = blk + kRedHeader;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) *counter(13) = (unsigned long long)res_rows;     // (diagnostic: last_gn_stats)
+    if (blockIdx.x == 0 && threadIdx.x == 0) *gn_counter(counters, kWsResidualRows) = (unsigned long long)res_rows;     // (diagnostic: last_gn_stats)
   }
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   d2* __restrict__ my_out = lds_out[wv];
@@ -1281,8 +1300,8 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_shortcut_kernel(const void* __
   const bool has_mask = mask_max != nullptr;
   const double thresh = has_mask ? mask_frac * mask_max[0] : 0.0;
   const int in_stride = tl.transposed ? tl.rows : 1, out_stride = tl.transposed ? tl.channels : 0;
-  const bool exact_exit = (flags & 1) != 0, confirm_walk = (flags & 4) != 0;
-  const int batch = ((flags >> 8) & 0xFFF) > 0 ? ((flags >> 8) & 0xFFF) : 1;
+  const bool exact_exit = (flags & kFlagExactExit) != 0, confirm_walk = (flags & kFlagConfirm) != 0;
+  const int batch = gn_batch(flags);
   int q_next = 0, q_end = 0;
   bool exhausted = false;
   unsigned handed = 0u;
@@ -1295,12 +1314,11 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_shortcut_kernel(const void* __
     if (q_next >= q_end) {
       long long t = 0;
       if (lane == 0) {
-        t = (long long)atomicAdd(counter(11), (unsigned long long)batch);
-        if (handed) atomicAdd(counter(10), (unsigned long long)handed);
+        t = (long long)atomicAdd(gn_counter(counters, kWsQueueHead), (unsigned long long)batch);
+        if (handed) atomicAdd(gn_counter(counters, kWsProgress), (unsigned long long)handed);
       }
       handed = 0u;
-      t = ((long long)__builtin_amdgcn_readfirstlane((int)(t >> 32)) << 32) |
-          (long long)(unsigned)__builtin_amdgcn_readfirstlane((int)t);
+      t = gn_uniform(t);
       if (t >= tl.n_tiles) { exhausted = true; return -1; }
       q_next = (int)t;
       q_end = t + batch < tl.n_tiles ? (int)t + batch : (int)tl.n_tiles;
@@ -1320,7 +1338,7 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_shortcut_kernel(const void* __
     int it = 0, warm = -1;                // warm >= 0: a continued pixel: its entry, + 256 if it continues after ONE step
     long long h0[kGnHistory], h1[kGnHistory];
 #pragma unroll
-    for (int k = 0; k < kGnHistory; ++k) { h0[k] = 0; h1[k] = 0; }
+  for (int k = 0; k < kGnHistory; ++k) { h0[k] = 0; h1[k] = 0; }
     for (;;) {
       const unsigned long long want = __ballot(po < 0);
       if (head < n_stash && want != 0ull) {
@@ -1483,8 +1501,8 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_shortcut_kernel(const void* __
   }
   if (n_stash > 0) drain();
   if (lane == 0) {
-    atomicAdd(counter(9), n_exec);                                // one atomic per wave
-    if (handed) atomicAdd(counter(10), (unsigned long long)handed);
+    atomicAdd(gn_counter(counters, kWsExecuted), n_exec);                                // one atomic per wave
+    if (handed) atomicAdd(gn_counter(counters, kWsProgress), (unsigned long long)handed);
   }
 }
 
@@ -1509,13 +1527,12 @@ __global__ __launch_bounds__(kCoopWaves * kWave, 3) void gn_coop_kernel(const vo
                                                                      const double* __restrict__ mask_max, double mask_frac,
                                                                      int flags, double stop_tol, double* __restrict__ out_a,
                                                                      unsigned long long* __restrict__ counters) {
-  auto counter = [&](int k) { return counters + (k - 9); };
   __shared__ double lds_pow[kPowN];                                      // 16 KB
   __shared__ double lds_part[kCoopWaves][12][kWave];                     // 24 KB: the partial sums of one step
   __shared__ long long lds_tile[2];
   for (int j = threadIdx.x; j < kPowN; j += kCoopWaves * kWave) lds_pow[j] = pow_entry(j);
   __syncthreads();
-  const EnergyClasses ec{(int)ws[1], (int)ws[4], (int)ws[2], (int)ws[5], (int)ws[3], (int)ws[6], ws[7], ws[8]};
+  const EnergyClasses ec = gn_energy_classes(ws);
   const double* __restrict__ tab = ws + kWsHeader;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const bool writer = wave == 0;                                         // wave 0 talks to memory (results, queue, counters)
@@ -1542,17 +1559,16 @@ __global__ __launch_bounds__(kCoopWaves * kWave, 3) void gn_coop_kernel(const vo
         if (exhausted) break;
         // one tile id for the whole workgroup: fetched by wave 0, read by all (two LDS words used in turn: a wave that runs
         // ahead to the NEXT fetch writes the other word, and cannot reach the one after before everybody has passed this barrier)
-        if (writer && lane == 0) lds_tile[fetches & 1] = (long long)atomicAdd(counter(11), 1ull);
+        if (writer && lane == 0) lds_tile[fetches & 1] = (long long)atomicAdd(gn_counter(counters, kWsQueueHead), 1ull);
         __syncthreads();
         long long t = lds_tile[fetches & 1];
-        t = ((long long)__builtin_amdgcn_readfirstlane((int)(t >> 32)) << 32) |
-            (long long)(unsigned)__builtin_amdgcn_readfirstlane((int)t);
+        t = gn_uniform(t);
         ++fetches;
         if (t >= tl.n_tiles) { exhausted = true; break; }
-        if (flags & 2) t = gn_tile_order(counters, n_e)[t];
+        if (flags & kFlagSorted) t = gn_tile_order(counters, n_e)[t];
         ct = gn_decode_tile(tl, n_pix, t);
         next_j = 0;
-        if (writer && lane == 0) atomicAdd(counter(10), (unsigned long long)(ct.nr * ct.nc));
+        if (writer && lane == 0) atomicAdd(gn_counter(counters, kWsProgress), (unsigned long long)(ct.nr * ct.nc));
       }
       const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(want >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)want, 0u));
       const int j = next_j + rank;
@@ -1602,13 +1618,13 @@ __global__ __launch_bounds__(kCoopWaves * kWave, 3) void gn_coop_kernel(const vo
     const GnSums s{{tot[0], tot[1]}, {tot[2], tot[3]}, {tot[4], tot[5]}, {tot[6], tot[7]}, {tot[8], tot[9]}, {tot[10], tot[11]}};
     double n0 = a0, n1 = a1;
     newton_solve_f64(s, gd0, gd1, n0, n1);
-    const bool advance = gn_exit_or_advance(n0, n1, n_iters, flags & 1, stop_tol, a0, a1, it, h0, h1, nullptr, (flags & 4) != 0);
+    const bool advance = gn_exit_or_advance(n0, n1, n_iters, flags & kFlagExactExit, stop_tol, a0, a1, it, h0, h1, nullptr, (flags & kFlagConfirm) != 0);
     if (pout >= 0 && (!advance || it >= n_iters)) {
       if (writer) store_a(out_a, pout, a0, a1);
       pout = -1;
     }
   }
-  if (writer && lane == 0) atomicAdd(counter(9), (unsigned long long)n_exec);
+  if (writer && lane == 0) atomicAdd(gn_counter(counters, kWsExecuted), (unsigned long long)n_exec);
 }
 
 __global__ __launch_bounds__(256) void mask_kernel(const void* __restrict__ g1, int g_is_f64, int64_t n_pix,
@@ -1742,6 +1758,110 @@ __global__ __launch_bounds__(256) void gn_model_sums_kernel(const double* __rest
   }
 }
 
+// ---- the host half of dexct_gn_decompose: tiling, argument checks, tile sort, grid --------------------------------------------
+
+// Order of the results: the pixels' own, or [..][row][channel] for pixels given as [..][channel][row] (options->out_rows /
+// out_channels).  n_tiles = -1 where the two do not describe the pixels (gn_check_call reports it).
+static GnTiling gn_tiling(int64_t n_pix, const dexct_gn_options* options) {
+  GnTiling tl{(n_pix + kTilePix - 1) / kTilePix, 0, 1, 1, 1, 1, 1u, 0u, 1u, 0u};
+  if (options && (options->out_rows != 0 || options->out_channels != 0)) {
+    const int64_t R = options->out_rows, C = options->out_channels;
+    if (R < 1 || C < 1 || n_pix % (R * C) != 0) return GnTiling{-1, 0, 1, 1, 1, 1, 1u, 0u, 1u, 0u};
+    tl.transposed = 1;
+    tl.rows = (int)R;
+    tl.channels = (int)C;
+    tl.tiles_r = (int)((R + kTileR - 1) / kTileR);
+    tl.tiles_c = (int)((C + kTileC - 1) / kTileC);
+    tl.n_tiles = (n_pix / (R * C)) * tl.tiles_r * tl.tiles_c;
+    gn_magic((unsigned)tl.tiles_r, &tl.mul_r, &tl.sh_r);
+    gn_magic((unsigned)tl.tiles_c, &tl.mul_c, &tl.sh_c);
+  }
+  return tl;
+}
+
+// DEXCT_OK, or what is wrong with a call: the first failing check decides the code.
+static int gn_check_call(const void* g1, const void* g2, int64_t n_pix, const double* i0, const double* mus, int32_t n_energies,
+                         int32_t n_bins, int32_t bin_div, int32_t n_iters, int32_t precision, int32_t n_polish, const double* out_a,
+                         const dexct_gn_options* options, const void* workspace, const GnTiling& tl) {
+  if (!g1 || !g2 || !i0 || !mus || !out_a || !workspace || n_pix <= 0 || n_energies <= 0 || n_iters < 0) return DEXCT_EINVAL;
+  if (n_bins < 1 || bin_div < 1 || n_bins > 65535) return DEXCT_EINVAL;
+  if (precision != 0 && precision != 1) return DEXCT_EINVAL;
+  if (precision == 1 && n_bins > 1) return DEXCT_EINVAL;   // mixed precision only with one shared spectrum
+  if (n_polish < 0) return DEXCT_EINVAL;
+  if (reinterpret_cast<uintptr_t>(out_a) & 15u) return DEXCT_EINVAL;      // a pixel's two doubles leave as one 16-byte store
+  if (n_energies > 4096) return DEXCT_ERANGE;
+  if ((n_pix + kGnBlock - 1) / kGnBlock > 0x7FFFFFFFll) return DEXCT_ERANGE;
+  if (tl.n_tiles < 0) return DEXCT_EINVAL;
+  if (tl.n_tiles > 0x7FFFFFFFll) return DEXCT_ERANGE;
+  if (options && (options->kernel < 0 || options->kernel > 2)) return DEXCT_EINVAL;
+  // the step-counting launch and the short cut (see gn_refill_kernel<true>, gn_shortcut_kernel): lane kernels, one shared
+  // spectrum, float64, step counts in a byte
+  const int pass = options ? options->pass : 0;
+  if (pass < 0 || pass > 2) return DEXCT_EINVAL;
+  if (pass != 0 && (n_bins > 1 || precision != 0 || n_iters > 254 || options->kernel == 2)) return DEXCT_EINVAL;
+  if (pass == DEXCT_GN_PASS_COUNT && (!options->iterations || options->start)) return DEXCT_EINVAL;
+  if (pass == DEXCT_GN_PASS_SHORTCUT && (!options->start || options->iterations)) return DEXCT_EINVAL;
+  if (pass == DEXCT_GN_PASS_SHORTCUT && (reinterpret_cast<uintptr_t>(options->start) & 15u)) return DEXCT_EINVAL;   // its pairs are read with 16-byte loads
+  if (options && (options->flags & ~(DEXCT_GN_FLAG_FULL_LOOP | DEXCT_GN_FLAG_NATURAL_ORDER | DEXCT_GN_FLAG_ONE_STEP | DEXCT_GN_FLAG_FULL_RESIDUAL))) return DEXCT_EINVAL;
+  if (options && (options->flags & DEXCT_GN_FLAG_ONE_STEP) && pass != DEXCT_GN_PASS_SHORTCUT) return DEXCT_EINVAL;
+  if (options && (options->flags & DEXCT_GN_FLAG_FULL_RESIDUAL) && !(options->flags & DEXCT_GN_FLAG_ONE_STEP)) return DEXCT_EINVAL;
+  if (options && options->blocks_per_cu < 0) return DEXCT_EINVAL;
+  return DEXCT_OK;
+}
+
+// The order of the hand-out on small sinograms (gn_tile_key_kernel): three launches that leave the permutation where
+// gn_tile_order finds it.
+static int gn_sort_tiles(const void* g1, int32_t g_is_f64, int64_t n_pix, const GnTiling& tl, const double* mask_max, double mask_frac,
+                         void* workspace, int32_t n_energies, int32_t n_bins, hipStream_t st) {
+  char* base = reinterpret_cast<char*>(workspace) + gn_ws_tables_bytes(n_energies, n_bins);
+  int* hist = reinterpret_cast<int*>(base);
+  int* ord = hist + kSortBuckets;
+  unsigned short* keys = reinterpret_cast<unsigned short*>(ord + kMaxSortTiles);
+  hipLaunchKernelGGL(gn_tile_key_kernel, dim3((unsigned)((tl.n_tiles + 63) / 64)), dim3(256), 0, st, g1, g_is_f64,
+                     (long long)n_pix, tl, mask_max, mask_frac, hist, keys);
+  DEXCT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gn_tile_scan_kernel, dim3(1), dim3(1024), 0, st, hist);
+  DEXCT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gn_tile_scatter_kernel, dim3((unsigned)((tl.n_tiles + 255) / 256)), dim3(256), 0, st, (int)tl.n_tiles, hist,
+                     (const unsigned short*)keys, ord);
+  DEXCT_LAUNCH_CHECK();
+  return DEXCT_OK;
+}
+
+// Workgroups of a queue kernel and the tiles a wave reserves per atomic on the queue head.
+// Lane refill from a queue of 64-pixel tiles; no more workgroups than can be resident: 28 - 35 KB of LDS and the registers
+// allow 4 per CU, 3 of the cooperative kernel (those beyond would start when the queue is already empty).  Round 3 measured the
+// fetch size: 64 / 128 / 256 / 512 / 1024 pixels = 766 / 764 / 769 / 771 / 773 ms on the benchmark sinograms and 64 ahead below 1e8
+// pixels (tools/probes/gn_small2.py): the tail of a launch is the last fetches' slowest pixels.
+// Tiles per reservation: 1 for the single launch (measured in round 3: larger fetches gain nothing at ~17 steps per pixel and
+// lengthen the tail).  On the short cut (two steps per pixel) the one word all waves of the chip queue for is the limit (12 ns
+// per atomic): 2 / 4 / 8 tiles per reservation once a wave gets 3 / 8 / 128 tiles on average (tools/probes/gn_tpf_small.py, 1 / 2 /
+// 4 / 8 tiles: 1200 x 800: 0.69 / 0.57 / 0.60 / 0.74 ms; 2.6e6 pixels: 1.29 / 0.85 / 0.82 / 0.84; 1.2e7: 4.75 / 2.62 / 2.49 / 2.55;
+// 250 views of the benchmark: 38.7 / 20.4 / 17.7 / 17.6); DEXCT_GN_TILES_PER_FETCH overrides
+struct GnGrid { int64_t blocks; int tiles_per_fetch; };
+
+static GnGrid gn_grid(const GnTiling& tl, int pass, bool coop, const dexct_gn_options* options, const GnEnv& env) {
+  static const int n_cu = [] {             // queried once per process (one GPU per process)
+    int dev_id = 0, n = 0;
+    if (hipGetDevice(&dev_id) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev_id) != hipSuccess || n <= 0)
+      n = 256;
+    return n;
+  }();
+  const int per_cu = (options && options->blocks_per_cu > 0) ? options->blocks_per_cu : env.blocks_per_cu;
+  if (coop) {                              // one tile per fetch, a workgroup per tile
+    const int64_t cap = (int64_t)n_cu * (per_cu > 0 ? per_cu : 3);
+    return GnGrid{tl.n_tiles > cap ? cap : tl.n_tiles, 1};
+  }
+  const int64_t cap = (int64_t)n_cu * (per_cu > 0 ? per_cu : 4);
+  int64_t nb = (tl.n_tiles + kGnBlock / kWave - 1) / (kGnBlock / kWave);
+  if (nb > cap) nb = cap;
+  const int64_t tiles_per_wave = tl.n_tiles / (nb * (kGnBlock / kWave));
+  int tiles_per_fetch = pass != DEXCT_GN_PASS_SHORTCUT ? 1 : (tiles_per_wave >= 128 ? 8 : tiles_per_wave >= 8 ? 4 : tiles_per_wave >= 3 ? 2 : 1);
+  if (env.tiles_per_fetch >= 1) tiles_per_fetch = env.tiles_per_fetch;
+  return GnGrid{nb, tiles_per_fetch};
+}
+
 extern "C" {
 
 int64_t dexct_gn_workspace_bytes(int32_t n_energies, int32_t n_bins) {
@@ -1754,131 +1874,57 @@ int dexct_gn_decompose(const void* g1, const void* g2, int32_t g_is_f64, int64_t
                        const double* mus, int32_t n_energies, int32_t n_bins, int32_t bin_div, int32_t n_iters,
                        int32_t precision, int32_t n_polish, const double* mask_max, double mask_frac, double* out_a,
                        const dexct_gn_options* options, void* workspace, void* stream) {
-  if (!g1 || !g2 || !i0 || !mus || !out_a || !workspace || n_pix <= 0 || n_energies <= 0 || n_iters < 0)
-    return DEXCT_EINVAL;
-  if (n_bins < 1 || bin_div < 1 || n_bins > 65535) return DEXCT_EINVAL;
-  if (precision != 0 && precision != 1) return DEXCT_EINVAL;
-  if (precision == 1 && n_bins > 1) return DEXCT_EINVAL;   // mixed precision only with one shared spectrum
-  if (n_polish < 0) return DEXCT_EINVAL;
-  if (reinterpret_cast<uintptr_t>(out_a) & 15u) return DEXCT_EINVAL;      // a pixel's two doubles leave as one 16-byte store
-  if (n_energies > 4096) return DEXCT_ERANGE;
-  const int64_t nblk = (n_pix + kGnBlock - 1) / kGnBlock;
-  if (nblk > 0x7FFFFFFFll) return DEXCT_ERANGE;
-  // order of the results: the pixels' own, or [..][row][channel] for pixels given as [..][channel][row]
-  GnTiling tl{(n_pix + kTilePix - 1) / kTilePix, 0, 1, 1, 1, 1, 1u, 0u, 1u, 0u};
-  if (options && (options->out_rows != 0 || options->out_channels != 0)) {
-    const int64_t R = options->out_rows, C = options->out_channels;
-    if (R < 1 || C < 1 || n_pix % (R * C) != 0) return DEXCT_EINVAL;
-    tl.transposed = 1;
-    tl.rows = (int)R;
-    tl.channels = (int)C;
-    tl.tiles_r = (int)((R + kTileR - 1) / kTileR);
-    tl.tiles_c = (int)((C + kTileC - 1) / kTileC);
-    tl.n_tiles = (n_pix / (R * C)) * tl.tiles_r * tl.tiles_c;
-    gn_magic((unsigned)tl.tiles_r, &tl.mul_r, &tl.sh_r);
-    gn_magic((unsigned)tl.tiles_c, &tl.mul_c, &tl.sh_c);
-  }
-  if (tl.n_tiles > 0x7FFFFFFFll) return DEXCT_ERANGE;
-  if (options && (options->kernel < 0 || options->kernel > 2)) return DEXCT_EINVAL;
-  // the step-counting launch and the short cut (see gn_refill_kernel<true>, gn_shortcut_kernel): lane kernels, one shared
-  // spectrum, float64, step counts in a byte
-  const int pass = options ? options->pass : 0;
-  if (pass < 0 || pass > 2) return DEXCT_EINVAL;
-  if (pass != 0 && (n_bins > 1 || precision != 0 || n_iters > 254 || options->kernel == 2)) return DEXCT_EINVAL;
-  if (pass == DEXCT_GN_PASS_COUNT && (!options->iterations || options->start)) return DEXCT_EINVAL;
-  if (pass == DEXCT_GN_PASS_SHORTCUT && (!options->start || options->iterations)) return DEXCT_EINVAL;
+  const GnTiling tl = gn_tiling(n_pix, options);
+  if (const int err = gn_check_call(g1, g2, n_pix, i0, mus, n_energies, n_bins, bin_div, n_iters, precision, n_polish, out_a, options,
+                                    workspace, tl))
+    return err;
+  const int pass = options ? options->pass : 0, oflags = options ? options->flags : 0;
   const double* start = (pass == DEXCT_GN_PASS_SHORTCUT) ? options->start : nullptr;
-  if (start && (reinterpret_cast<uintptr_t>(start) & 15u)) return DEXCT_EINVAL;   // its pairs are read with 16-byte loads
-  if (options && (options->flags & ~(DEXCT_GN_FLAG_FULL_LOOP | DEXCT_GN_FLAG_NATURAL_ORDER | DEXCT_GN_FLAG_ONE_STEP | DEXCT_GN_FLAG_FULL_RESIDUAL))) return DEXCT_EINVAL;
-  if (options && (options->flags & DEXCT_GN_FLAG_ONE_STEP) && pass != DEXCT_GN_PASS_SHORTCUT) return DEXCT_EINVAL;
-  if (options && (options->flags & DEXCT_GN_FLAG_FULL_RESIDUAL) && !(options->flags & DEXCT_GN_FLAG_ONE_STEP)) return DEXCT_EINVAL;
-  if (options && options->blocks_per_cu < 0) return DEXCT_EINVAL;
   hipStream_t st = as_stream(stream);
   double* ws = reinterpret_cast<double*>(workspace);
   hipLaunchKernelGGL(gn_tables_kernel, dim3(n_bins), dim3(256), 0, st, i0, mus, n_energies, n_bins, ws);
   DEXCT_LAUNCH_CHECK();
   const GnEnv& env = gn_env();
-  const int oflags = options ? options->flags : 0;
   // DEXCT_GN_FLAG_FULL_LOOP (or DEXCT_GN_FULL_LOOP=1 at process start) runs every iteration: the check that the repeated-state
   // exit changes no bit
-  const int exact_exit = ((oflags & DEXCT_GN_FLAG_FULL_LOOP) || env.full_loop) ? 0 : 1;
+  const int exact_exit = ((oflags & DEXCT_GN_FLAG_FULL_LOOP) || env.full_loop) ? 0 : kFlagExactExit;
   // The tolerance stop.  options->stop_tol >= 0 is taken as given (0 = the reference's fixed count, bit for bit);
   // negative or no options = the library default: 1e-12, or DEXCT_GN_STOP_TOL, or 0 with DEXCT_GN_EXACT=1 (read once).
   double tol = options ? options->stop_tol : -1.0;
   if (!(tol >= 0.0)) tol = env.default_tol;
   if (!exact_exit) tol = 0.0;                         // the full loop is the full loop
-  // a walk from the reference's start value ends by the tolerance rule only when the step before contracted too (gn_converged)
-  const int confirm_flag = 4;
   if (pass != 0 && !(tol > 0.0)) return DEXCT_EINVAL;  // both passes end pixels by the tolerance rule
-  const dim3 grid((unsigned)nblk), block(kGnBlock);
+  // (kFlagConfirm: a walk from the reference's start value ends by the tolerance rule only when the step before contracted too)
+  const dim3 grid((unsigned)((n_pix + kGnBlock - 1) / kGnBlock)), block(kGnBlock);
   if (n_bins > 1) {
     hipLaunchKernelGGL((gn_kernel<false, true>), grid, block, 0, st, g1, g2, g_is_f64, n_pix, (const double*)ws,
-                       n_energies, n_iters, 0, n_bins, bin_div, mask_max, mask_frac, exact_exit | confirm_flag, tol, tl, out_a);
+                       n_energies, n_iters, 0, n_bins, bin_div, mask_max, mask_frac, exact_exit | kFlagConfirm, tol, tl, out_a);
   } else if (precision == 0) {
-    // Lane refill from a queue of 64-pixel tiles; no more workgroups than can be resident: 28 - 35 KB of LDS and the registers
-    // allow 4 per CU (those beyond would start when the queue is already empty).  Round 3 measured the fetch size: 64 / 128 /
-    // 256 / 512 / 1024 pixels = 766 / 764 / 769 / 771 / 773 ms on the benchmark sinograms and 64 ahead below 1e8 pixels
-    // (tools/probes/gn_small2.py): the tail of a launch is the last fetches' slowest pixels.
-    static const int n_cu = [] {             // queried once per process (one GPU per process)
-      int dev_id = 0, n = 0;
-      if (hipGetDevice(&dev_id) != hipSuccess ||
-          hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev_id) != hipSuccess || n <= 0)
-        n = 256;
-      return n;
-    }();
-    const int per_cu = (options && options->blocks_per_cu > 0) ? options->blocks_per_cu : env.blocks_per_cu;
-    const int64_t cap = (int64_t)n_cu * (per_cu > 0 ? per_cu : 4);
-    int64_t nb = (tl.n_tiles + kGnBlock / kWave - 1) / (kGnBlock / kWave);
-    if (nb > cap) nb = cap;
-    unsigned long long* counters = reinterpret_cast<unsigned long long*>(ws) + 9;
-    // the cooperative kernel below DEXCT_GN_COOP_BELOW pixels (options->kernel: 1 / 2 force one or the other)
-    const int which = options ? options->kernel : 0;
+    const int which = options ? options->kernel : 0;     // 1 / 2 force the lane / the cooperative kernel
+    const bool coop = pass == 0 && (which == 2 || (which == 0 && n_pix < env.coop_below));
+    const GnGrid gg = gn_grid(tl, pass, coop, options, env);
+    unsigned long long* counters = reinterpret_cast<unsigned long long*>(ws) + kWsExecuted;
     // small sinograms: thick tiles first (DEXCT_GN_FLAG_NATURAL_ORDER / DEXCT_GN_SORT=0 keep the natural order)
-    const int* order = nullptr;
+    bool sorted = false;
     if (pass == 0 && tl.n_tiles <= kMaxSortTiles && tl.n_tiles > 1 && env.sort && !(oflags & DEXCT_GN_FLAG_NATURAL_ORDER)) {
-      char* base = reinterpret_cast<char*>(workspace) + gn_ws_tables_bytes(n_energies, n_bins);
-      int* hist = reinterpret_cast<int*>(base);
-      int* ord = hist + kSortBuckets;
-      unsigned short* keys = reinterpret_cast<unsigned short*>(ord + kMaxSortTiles);
-      hipLaunchKernelGGL(gn_tile_key_kernel, dim3((unsigned)((tl.n_tiles + 63) / 64)), dim3(256), 0, st, g1, g_is_f64,
-                         (long long)n_pix, tl, mask_max, mask_frac, hist, keys);
-      DEXCT_LAUNCH_CHECK();
-      hipLaunchKernelGGL(gn_tile_scan_kernel, dim3(1), dim3(1024), 0, st, hist);
-      DEXCT_LAUNCH_CHECK();
-      hipLaunchKernelGGL(gn_tile_scatter_kernel, dim3((unsigned)((tl.n_tiles + 255) / 256)), dim3(256), 0, st, (int)tl.n_tiles, hist,
-                         (const unsigned short*)keys, ord);
-      DEXCT_LAUNCH_CHECK();
-      order = ord;
+      if (const int err = gn_sort_tiles(g1, g_is_f64, n_pix, tl, mask_max, mask_frac, workspace, n_energies, n_bins, st)) return err;
+      sorted = true;
     }
-    // tiles a wave reserves per atomic on the queue head: 1 for the single launch (measured in round 3: larger fetches gain
-    // nothing at ~17 steps per pixel and lengthen the tail).  On the short cut (two steps per pixel) the one word all
-    // waves of the chip queue for is the limit (12 ns per atomic): 2 / 4 / 8 tiles per reservation once a wave gets 3 / 8 / 128
-    // tiles on average (tools/probes/gn_tpf_small.py, 1 / 2 / 4 / 8 tiles: 1200 x 800: 0.69 / 0.57 / 0.60 / 0.74 ms; 2.6e6 pixels:
-    // 1.29 / 0.85 / 0.82 / 0.84; 1.2e7: 4.75 / 2.62 / 2.49 / 2.55; 250 views of the benchmark: 38.7 / 20.4 / 17.7 / 17.6);
-    // DEXCT_GN_TILES_PER_FETCH overrides
-    const int64_t tiles_per_wave = tl.n_tiles / (nb * (kGnBlock / kWave));
-    int tiles_per_fetch = pass != DEXCT_GN_PASS_SHORTCUT ? 1 : (tiles_per_wave >= 128 ? 8 : tiles_per_wave >= 8 ? 4 : tiles_per_wave >= 3 ? 2 : 1);
-    if (env.tiles_per_fetch >= 1) tiles_per_fetch = env.tiles_per_fetch;
-    const int kflags = exact_exit | (order ? 2 : 0) | confirm_flag | (tiles_per_fetch << 8);
+    const int kflags = exact_exit | (sorted ? kFlagSorted : 0) | kFlagConfirm | (coop ? 0 : gg.tiles_per_fetch << kFlagFetchShift);
+    auto launch = [&](auto kernel, int threads, int flags, auto... last) {      // the queue kernels share their arguments up to `counters`
+      hipLaunchKernelGGL(kernel, dim3((unsigned)gg.blocks), dim3(threads), 0, st, g1, g2, g_is_f64, (long long)n_pix, (const double*)ws,
+                         n_energies, n_iters, tl, mask_max, mask_frac, flags, tol, out_a, counters, last...);
+    };
     if (pass == DEXCT_GN_PASS_COUNT)
-      hipLaunchKernelGGL((gn_refill_kernel<true>), dim3((unsigned)nb), block, 0, st, g1, g2, g_is_f64, (long long)n_pix,
-                         (const double*)ws, n_energies, n_iters, tl, mask_max, mask_frac, kflags, tol, out_a, counters, options->iterations);
+      launch(gn_refill_kernel<true>, kGnBlock, kflags, options->iterations);
     else if (pass == DEXCT_GN_PASS_SHORTCUT && (oflags & DEXCT_GN_FLAG_ONE_STEP))
-      hipLaunchKernelGGL(gn_shortcut_kernel<1>, dim3((unsigned)nb), block, 0, st, g1, g2, g_is_f64, (long long)n_pix,
-                         (const double*)ws, n_energies, n_iters, tl, mask_max, mask_frac,
-                         kflags | ((env.reduced && !(oflags & DEXCT_GN_FLAG_FULL_RESIDUAL)) ? kFlagReduced : 0), tol, out_a, counters, start);
+      launch(gn_shortcut_kernel<1>, kGnBlock, kflags | ((env.reduced && !(oflags & DEXCT_GN_FLAG_FULL_RESIDUAL)) ? kFlagReduced : 0), start);
     else if (pass == DEXCT_GN_PASS_SHORTCUT)
-      hipLaunchKernelGGL(gn_shortcut_kernel<2>, dim3((unsigned)nb), block, 0, st, g1, g2, g_is_f64, (long long)n_pix,
-                         (const double*)ws, n_energies, n_iters, tl, mask_max, mask_frac, kflags, tol, out_a, counters, start);
-    else if (which == 2 || (which == 0 && n_pix < env.coop_below)) {
-      int64_t ncb = tl.n_tiles;
-      const int64_t ccap = (int64_t)n_cu * (per_cu > 0 ? per_cu : 3);
-      if (ncb > ccap) ncb = ccap;
-      hipLaunchKernelGGL(gn_coop_kernel, dim3((unsigned)ncb), dim3(kCoopWaves * kWave), 0, st, g1, g2, g_is_f64, (long long)n_pix,
-                         (const double*)ws, n_energies, n_iters, tl, mask_max, mask_frac, exact_exit | (order ? 2 : 0) | confirm_flag, tol, out_a, counters);
-    } else
-      hipLaunchKernelGGL((gn_refill_kernel<false>), dim3((unsigned)nb), block, 0, st, g1, g2, g_is_f64, (long long)n_pix,
-                         (const double*)ws, n_energies, n_iters, tl, mask_max, mask_frac, kflags, tol, out_a, counters, nullptr);
+      launch(gn_shortcut_kernel<2>, kGnBlock, kflags, start);
+    else if (coop)
+      launch(gn_coop_kernel, kCoopWaves * kWave, kflags);
+    else
+      launch(gn_refill_kernel<false>, kGnBlock, kflags, (unsigned char*)nullptr);
   } else {
     hipLaunchKernelGGL((gn_kernel<true, false>), grid, block, 0, st, g1, g2, g_is_f64, n_pix, (const double*)ws,
                        n_energies, n_iters, n_polish, 1, 1, mask_max, mask_frac, exact_exit, 0.0, tl, out_a);

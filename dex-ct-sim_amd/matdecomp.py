@@ -147,12 +147,17 @@ class GnAuditError(RuntimeError):
     pass
 
 
-_last_ws = []          # workspaces of the most recent call (one per view chunk of the pipelined boundary)
-_last_events = []      # (before, after) events of the launches of the most recent call(s)
-_last_zeroed = None
-_last_mode = 'single'
-_last_audit = None
-_last_ne = 0
+class _GnRun:
+    """What the most recent gn_device call left for diagnostics - or, with ``accumulate_stats``, ALL the chunk launches of a
+    pipelined get_basismat_sinos call: per launch its workspace and its (before, after) events; of the latest launch the event
+    recorded after its counters were zeroed, the mode and the tables' n_e; the sampled audit, if one ran."""
+    __slots__ = ('workspaces', 'events', 'zeroed', 'mode', 'n_energies', 'audit')
+
+    def __init__(self):
+        self.workspaces, self.events, self.zeroed, self.mode, self.n_energies, self.audit = [], [], None, 'single', 0, None
+
+
+_last_run = None       # the process's only diagnostic state: None before the first call
 _table_cache = {}
 
 
@@ -165,17 +170,24 @@ def last_gn_stats():
     pair)'; ``audit``: the last sampled audit, if any.  ``residual_energies``: the table rows the chord residual of the one-step
     launch summed per pixel, as the kernel reports it - the rows of the reduced residual rule where one is installed and not
     switched off, else (and in every other mode) the tables' n_e."""
-    if not _last_ws:
+    return _gn_stats(_last_run)
+
+
+def _gn_stats(run):
+    """last_gn_stats() of a _GnRun (None: no call yet); reads the workspaces' words, touches nothing else."""
+    if run is None or not run.workspaces:
         return None
-    stacked = torch.stack([w[72:112].view(torch.int64) for w in _last_ws])
-    words = stacked[:, :4].sum(dim=0).tolist()
-    st = {'pixel_iterations': int(words[0]), 'stalled_lane_steps': int(words[3]), 'launches': len(_last_ws), 'mode': _last_mode,
-          'residual_energies': int(stacked[:, 4].max().item()) if _last_mode == 'one' else int(_last_ne)}
-    if _last_events:
+    stacked = torch.stack([w[_native.GN_WS_WORDS].view(torch.int64) for w in run.workspaces])      # [launch, word]
+    at = lambda offset: (offset - _native.GN_WS_EXECUTED) // 8
+    total = stacked.sum(dim=0).tolist()
+    st = {'pixel_iterations': int(total[at(_native.GN_WS_EXECUTED)]), 'stalled_lane_steps': int(total[at(_native.GN_WS_STALLS)]),
+          'launches': len(run.workspaces), 'mode': run.mode,
+          'residual_energies': int(stacked[:, at(_native.GN_WS_RESIDUAL_ROWS)].max().item()) if run.mode == 'one' else int(run.n_energies)}
+    if run.events:
         torch.cuda.synchronize()
-        st['main_ms'] = sum(e[0].elapsed_time(e[1]) for e in _last_events)
-    if _last_audit is not None:
-        st['audit'] = _last_audit
+        st['main_ms'] = sum(e[0].elapsed_time(e[1]) for e in run.events)
+    if run.audit is not None:
+        st['audit'] = run.audit
     return st
 
 
@@ -258,21 +270,27 @@ def _gate_cache_path(i0_h, mus_h, cal_tol):
     return os.path.join(d, f'gate_{h.hexdigest()[:32]}.npz')
 
 
+def _gate_digest(start_h, stats):
+    """The checksum a gate file carries of its own content."""
+    import hashlib
+    import json
+    blob = b'' if start_h is None else start_h.tobytes()
+    return hashlib.sha256(blob + json.dumps(stats, sort_keys=True).encode()).hexdigest()
+
+
 def _gate_from_disk(path, i0_h, mus_h):
     """(start, stats) of an earlier process, or None: the file must be complete, carry its own checksum and agree with the
     grid this process would lay out for the tables (a stale, truncated or foreign file is ignored, never trusted)."""
     if path is None or not os.path.exists(path):
         return None
     try:
-        import hashlib
         import json
         from . import quadrature
         with np.load(path, allow_pickle=False) as z:
             start_h = np.ascontiguousarray(z['start'], dtype=np.float64) if z['start'].size else None
             stats = json.loads(str(z['stats']))
             digest = str(z['digest'])
-        blob = b'' if start_h is None else start_h.tobytes()
-        if hashlib.sha256(blob + json.dumps(stats, sort_keys=True).encode()).hexdigest() != digest:
+        if _gate_digest(start_h, stats) != digest:
             return None
         if start_h is not None:
             pieces = quadrature.newton_start_grid(i0_h.reshape(2, -1), mus_h)
@@ -292,11 +310,9 @@ def _gate_to_disk(path, start_h, stats):
     if path is None:
         return
     try:
-        import hashlib
         import json
         os.makedirs(os.path.dirname(path), exist_ok=True)
-        blob = b'' if start_h is None else start_h.tobytes()
-        digest = hashlib.sha256(blob + json.dumps(stats, sort_keys=True).encode()).hexdigest()
+        digest = _gate_digest(start_h, stats)
         tmp = f'{path}.{os.getpid()}.tmp'
         with open(tmp, 'wb') as f:
             np.savez(f, start=np.zeros(0) if start_h is None else start_h, stats=json.dumps(stats, sort_keys=True), digest=digest)
@@ -344,8 +360,9 @@ def reduced_block(start, rule, mus):
     """The device start array ``start`` (with its power form, [10] = 2) with the rows of a reduced residual rule appended behind
     the power form and [10] set to 3 (csrc/gn.hip, kRedHeader; include/dexct.h): what gn_shortcut_kernel<1> then sums its chord
     residual over.  Everything before the appended block is unchanged."""
+    from . import quadrature
     n = int(start[3].item())
-    off = int(start[11].item()) + 72 * n * n
+    off = int(start[11].item()) + quadrature.POWER_CELL * n * n
     if not (start[10].item() == 2.0 and start[11].item() > 0.0 and off == start.numel()):
         raise ValueError('reduced_block needs a start array that ends with its power form')
     block = _native.gn_reduced_rows(_host_tables(mus), rule['nodes'], rule['w'])
@@ -421,12 +438,12 @@ def _device_tables(i0, mus, dev, want_gate, cal_tol=1.0e-12):
 _audit_calls = 0
 
 
-def _audit(g1, g2, a, i0, mus, n_iters, ppm, strict, out_rc, mask_max, mask_frac, merge=False):
+def _audit(run, g1, g2, a, i0, mus, n_iters, ppm, strict, out_rc, mask_max, mask_frac):
     """Sampled audit of a default-mode result ``a`` (see DEFAULT_AUDIT_PPM): re-solve ~ppm pixels per million with the
-    reference's fixed count (stop_tol = 0, the single launch) and compare.  ``merge``: add to the record of the call's earlier
-    chunks."""
-    global _last_audit, _audit_calls
-    before = _last_audit if merge else None
+    reference's fixed count (stop_tol = 0, the single launch) and compare.  The outcome becomes ``run.audit``, added to what
+    the run's earlier chunks left there."""
+    global _audit_calls
+    before = run.audit
     n_pix = g1.numel()
     m = int(min(max(round(n_pix * ppm * 1e-6), min(n_pix, 64)), n_pix, 1 << 22))
     gen = torch.Generator(device=g1.device)           # Philox on the device; another sample in every call, the same in every run
@@ -442,30 +459,26 @@ def _audit(g1, g2, a, i0, mus, n_iters, ppm, strict, out_rc, mask_max, mask_frac
     else:
         oidx = idx
     got = a.reshape(-1, 2)[oidx]
-    global _last_ws, _last_events, _last_mode
-    keep = (_last_ws, _last_events, _last_mode)
-    want = gn_device(s1, s2, i0, mus, n_iters, 'f64', mask_max=mask_max, mask_frac=mask_frac, stop_tol=0.0, kernel=1, two_level=False, audit=0)
-    _last_ws, _last_events, _last_mode = keep
+    want = _gn_launch(s1, s2, i0, mus, n_iters, 'f64', mask_max=mask_max, mask_frac=mask_frac, stop_tol=0.0, kernel=1, two_level=False)[0]
     rel = (got - want).abs() / want.abs().amax(dim=-1, keepdim=True).clamp(min=1.0)
     same_nan = torch.isnan(got) == torch.isnan(want)
     bad = (~same_nan.all(dim=-1)) | (torch.nan_to_num(rel, nan=0.0).amax(dim=-1) > AUDIT_TOL)
     n_bad = int(bad.sum().item())
     worst = float(torch.nan_to_num(rel, nan=0.0).max().item())
-    _last_audit = {'pixels': m + (before['pixels'] if before else 0), 'differing': n_bad + (before['differing'] if before else 0),
+    run.audit = {'pixels': m + (before['pixels'] if before else 0), 'differing': n_bad + (before['differing'] if before else 0),
                    'max_rel_diff': max(worst, before['max_rel_diff'] if before else 0.0), 'tolerance': AUDIT_TOL}
     if before and 'worst' in before:
-        _last_audit['worst'] = before['worst']
+        run.audit['worst'] = before['worst']
     if n_bad:
         k = int(torch.nan_to_num(rel, nan=float('inf')).amax(dim=-1).argmax().item())
         msg = (f'Newton short cut audit: {n_bad} of {m} sampled pixels differ from the reference\'s fixed iteration count by more than '
                f'{AUDIT_TOL:g} (or in their NaN pattern); worst: pixel {int(idx[k])} counts ({float(s1[k])!r}, {float(s2[k])!r}) '
                f'default {got[k].tolist()} exact {want[k].tolist()}.  Use stop_tol=0 / DEXCT_GN_EXACT=1 and report the tables.')
-        _last_audit['worst'] = {'pixel': int(idx[k]), 'counts': [float(s1[k]), float(s2[k])], 'default': got[k].tolist(), 'exact': want[k].tolist()}
+        run.audit['worst'] = {'pixel': int(idx[k]), 'counts': [float(s1[k]), float(s2[k])], 'default': got[k].tolist(), 'exact': want[k].tolist()}
         if strict:
             raise GnAuditError(msg)
         import warnings
         warnings.warn(msg, GnAuditWarning, stacklevel=3)
-    return _last_audit
 
 
 def gn_device(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=None, bin_div=1, mask_max=None,
@@ -487,6 +500,27 @@ def gn_device(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=N
     for the pair (quadrature.residual_rule), False = over all energies (so does DEXCT_GN_REDUCED=0 in the environment, read once by
     the library); last_gn_stats()['residual_energies'] says which it was.
     Returns a device tensor of shape g1.shape + (2,) float64 (with ``out_rc``: the last two sinogram dimensions swapped)."""
+    global _last_run
+    a, ws, ev, zeroed, mode, n_e = _gn_launch(g1, g2, i0, mus, n_iters, precision, n_polish, out, bin_div, mask_max, mask_frac, stop_tol,
+                                              out_rc, kernel, two_level, full_loop, natural_order, blocks_per_cu, reduced)
+    run = _last_run if accumulate_stats and _last_run is not None else _GnRun()
+    run.workspaces.append(ws)
+    run.events.append(ev)
+    run.zeroed, run.mode, run.n_energies = zeroed, mode, n_e
+    _last_run = run
+    ppm = DEFAULT_AUDIT_PPM if audit is None else float(audit)
+    if ppm > 0.0 and mode in SHORTCUT_MODES:
+        _audit(run, g1, g2, a, i0, mus, n_iters, ppm, DEFAULT_AUDIT_STRICT if audit_strict is None else bool(audit_strict),
+               None if out_rc is None else (int(out_rc[0]), int(out_rc[1])), mask_max, mask_frac)
+    return a
+
+
+def _gn_launch(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=None, bin_div=1, mask_max=None, mask_frac=0.95,
+               stop_tol=None, out_rc=None, kernel=0, two_level=None, full_loop=False, natural_order=False, blocks_per_cu=0,
+               reduced=None):
+    """One dexct_gn_decompose launch with gn_device's arguments (see there): everything up to and including the call.  Touches no
+    module state.  Returns (result, workspace, (before, after) events, the event recorded after the counters were zeroed, mode,
+    n_e)."""
     lib = _native.load()
     dev = g1.device
     precision = precision or DEFAULT_PRECISION
@@ -535,14 +569,12 @@ def gn_device(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=N
     a = out if out is not None else torch.empty(shape + (2,), dtype=torch.float64, device=dev)
     if out is not None and (a.numel() != 2 * g1.numel() or a.dtype != torch.float64 or not a.is_contiguous()):
         raise ValueError('out must be a contiguous float64 tensor with two values per pixel')
-    global _last_zeroed, _last_ws, _last_events, _last_mode, _last_audit, _last_ne
-    _last_ne = n_e
     is64 = int(g1.dtype == torch.float64)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     ws = torch.empty(lib.dexct_gn_workspace_bytes(n_e, n_bins), dtype=torch.uint8, device=dev)
-    ws[72:112].zero_()       # executed-iteration, progress, queue and stall counters (and the residual's row count): defined before anybody polls them
-    _last_zeroed = torch.cuda.Event()
-    _last_zeroed.record()    # a progress poller on another stream waits for this (never reads uninitialised bytes)
+    ws[_native.GN_WS_WORDS].zero_()       # executed-iteration, progress, queue and stall counters (and the residual's row count): defined before anybody polls them
+    zeroed = torch.cuda.Event()
+    zeroed.record()          # a progress poller on another stream waits for this (never reads uninitialised bytes)
     flags = ((_native.GN_FLAG_FULL_LOOP if full_loop else 0) | (_native.GN_FLAG_NATURAL_ORDER if natural_order else 0)
              | (_native.GN_FLAG_ONE_STEP if mode == 'one' else 0)
              | (_native.GN_FLAG_FULL_RESIDUAL if mode == 'one' and reduced is False else 0))
@@ -557,27 +589,19 @@ def gn_device(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=N
                                          opts, ptr(ws), stream_ptr()),
                   'dexct_gn_decompose')
     ev[1].record()
-    _last_ws = (_last_ws + [ws]) if accumulate_stats else [ws]
-    _last_events = (_last_events if accumulate_stats else []) + [ev]
-    _last_mode = mode
-    if not accumulate_stats:
-        _last_audit = None
-    ppm = DEFAULT_AUDIT_PPM if audit is None else float(audit)
-    if ppm > 0.0 and mode in SHORTCUT_MODES:
-        _audit(g1, g2, a, i0, mus, n_iters, ppm, DEFAULT_AUDIT_STRICT if audit_strict is None else bool(audit_strict),
-               (rows, chans) if out_rc is not None else None, mask_max, mask_frac, merge=accumulate_stats)
-    return a
+    return a, ws, ev, zeroed, mode, n_e
 
 
-def _progress_lines(ws, n_views, n_bins, done_event, t0, every=20, poll_s=0.05):
-    """The reference's progress line ``j / nViews t=...s`` (matdecomp.py:111-112, one per 20 views), driven by the
-    kernel's own finished-pixel counter (workspace byte 80), read on a side stream while the kernel runs."""
+def _progress_lines(run, n_views, n_bins, t0, every=20, poll_s=0.05):
+    """The reference's progress line ``j / nViews t=...s`` (matdecomp.py:111-112, one per 20 views), driven by the finished-pixel
+    counter (_native.GN_WS_PROGRESS) of the latest launch of ``run``, read on a side stream while the kernel runs."""
     import time
+    done_event = torch.cuda.Event()
+    done_event.record()
     side = torch.cuda.Stream()
-    if _last_zeroed is not None:
-        side.wait_event(_last_zeroed)
+    side.wait_event(run.zeroed)         # (never reads bytes the launch has not zeroed yet)
     host = torch.zeros(1, dtype=torch.int64).pin_memory()
-    counter = ws[80:88].view(torch.int64)
+    counter = run.workspaces[-1][_native.GN_WS_PROGRESS:_native.GN_WS_PROGRESS + 8].view(torch.int64)
     n_pix = n_views * max(n_bins, 1)
     next_view = 0
     while True:
@@ -618,22 +642,19 @@ def optimize_sino(Sino_gg, ee, i0, mus, n_iters, verbose=True, dtype=None, preci
     i0 = np.asarray(i0, dtype=np.float64)
     if i0.ndim == 3 and np.all(i0 == i0[:, :1, :]):
         i0 = i0[:, 0, :]                 # one spectrum tiled over the channels (:151): the fast path
+    solver = dict(precision=precision, stop_tol=stop_tol, two_level=two_level, audit=audit, audit_strict=audit_strict, **gn_knobs)
     if (int(np.shape(Sino_gg)[0]), int(np.shape(mus)[0])) != (2, 2):
         # more than two measurements or a third basis material: the general kernel (gn_device_multi)
-        return _optimize_sino_multi(Sino_gg, i0, mus, n_iters, dict(precision=precision, stop_tol=stop_tol, two_level=two_level,
-                                                                    audit=audit, audit_strict=audit_strict, **gn_knobs))
+        return _optimize_sino_multi(Sino_gg, i0, mus, n_iters, solver)
     if i0.ndim == 3 and i0.shape[1] != np.asarray(Sino_gg).shape[2]:
         raise ValueError('i0 has a different number of bins than the sinogram')
     dev = device()
     g = _as_device_counts(np.asarray(Sino_gg), dev)
     import time
     t0 = time.time()
-    a = gn_device(g[0], g[1], i0, np.asarray(mus, dtype=np.float64), n_iters, precision, stop_tol=stop_tol, two_level=two_level, audit=audit,
-                  audit_strict=audit_strict, **gn_knobs)          # (kernel, full_loop, natural_order, blocks_per_cu: see gn_device)
+    a = gn_device(g[0], g[1], i0, np.asarray(mus, dtype=np.float64), n_iters, **solver)      # (gn_knobs: kernel, full_loop, ..: see gn_device)
     if verbose:
-        done = torch.cuda.Event()
-        done.record()
-        _progress_lines(_last_ws[-1], int(g.shape[1]), int(g[0].numel() // max(int(g.shape[1]), 1)), done, t0)
+        _progress_lines(_last_run, int(g.shape[1]), int(g[0].numel() // max(int(g.shape[1]), 1)), t0)
     return to_host(a)
 
 
@@ -742,6 +763,28 @@ def _optimize_sino_multi(Sino_gg, i0, mus, n_iters, keywords):
     return to_host(gn_device_multi(g, i0, mus, n_iters, full_loop=bool(keywords.get('full_loop', False))))
 
 
+def _sino_max(lib, g):
+    """Device float64 scalar: the maximum of the counts ``g`` (what the air mask's threshold is a fraction of)."""
+    gmax = torch.empty((), dtype=torch.float64, device=g.device)
+    _native.check(lib.dexct_reduce_max(ptr(g), int(g.dtype == torch.float64), g.numel(), ptr(gmax), stream_ptr()), 'dexct_reduce_max')
+    return gmax
+
+
+def _raise_if_singular(a, n_iters, where=' on this rank', world=1):
+    """``strict``: SingularHessianError when a pixel of the result ``a`` ended non-finite (masked pixels are exactly 0, hence
+    finite).  ``world > 1``: the count is all-reduced, so that every rank raises, or none."""
+    bad = ~torch.isfinite(a).all(dim=-1)
+    n_bad = int(bad.sum().item())
+    if world > 1:
+        t = torch.tensor(float(n_bad), dtype=torch.float64, device='cpu' if torch.distributed.get_backend() == 'gloo' else a.device)
+        torch.distributed.all_reduce(t)
+        n_bad = int(t.item())
+    if n_bad:
+        first = bad.flatten().nonzero()[:1].flatten().tolist()
+        raise SingularHessianError(f'Singular matrix: {n_bad} pixel(s) outside the air mask ended non-finite '
+                                   f'after {n_iters} Newton iterations (first flat index{where}: {first})')
+
+
 def decomposition_tables(ct, spec1, spec2):
     """Union energy grid and effective spectra exactly as matdecomp.py:140-150 builds them."""
     ee = np.array(sorted(set(np.append(spec1.E, spec2.E))))
@@ -772,8 +815,7 @@ _PIPE_CHUNKS = 8                 # view chunks of the pipelined host boundary (t
 _PIPE_MIN_PIXELS = 1 << 24       # below 16.8 M pixels (64 MiB per float32 sinogram) the plain sequence is as fast
 
 
-def _basismat_sinos_pipelined(lib, dev, s1, s2, i0, mus, n_iters, mask_thresh, precision, strict, stop_tol, two_level=None, audit=None,
-                              audit_strict=None):
+def _basismat_sinos_pipelined(lib, dev, s1, s2, i0, mus, n_iters, mask_thresh, strict, solver):
     """get_basismat_sinos for NumPy sinograms of benchmark size: sinogram 1 goes to the device first (the mask needs its
     global maximum, matdecomp.py:195-196), then per view chunk: sinogram 2's chunk arrives on an upload stream, the Newton
     kernel runs on it, and the finished chunk leaves for page-locked host memory on a download stream while the next chunk
@@ -787,11 +829,11 @@ def _basismat_sinos_pipelined(lib, dev, s1, s2, i0, mus, n_iters, mask_thresh, p
         comp, up, down = side_streams(dev)
         comp.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(comp):
-            return _pipeline(lib, dev, a1, a2, i0, mus, n_iters, mask_thresh, precision, strict, stop_tol, two_level, audit, audit_strict,
-                             up, down)
+            return _pipeline(lib, dev, a1, a2, i0, mus, n_iters, mask_thresh, strict, solver, up, down)
 
 
-def _pipeline(lib, dev, a1, a2, i0, mus, n_iters, mask_thresh, precision, strict, stop_tol, two_level, audit, audit_strict, copy, down):
+def _pipeline(lib, dev, a1, a2, i0, mus, n_iters, mask_thresh, strict, solver, copy, down):
+    """``solver``: gn_device's solver keywords (get_basismat_sinos); ``copy`` / ``down``: the upload and the download stream."""
     dt = torch.float32 if a1.dtype == np.float32 else torch.float64
     h1 = torch.from_numpy(a1)
     h2 = torch.from_numpy(a2)
@@ -801,9 +843,7 @@ def _pipeline(lib, dev, a1, a2, i0, mus, n_iters, mask_thresh, precision, strict
     # behind the uploads of ALL later input chunks; the kernels run on the current stream, _device.side_streams)
     g1 = h1.to(dev, non_blocking=True)                      # (one DMA: the array is page-locked)
     g2 = torch.empty_like(g1)
-    gmax = torch.empty((), dtype=torch.float64, device=dev)
-    _native.check(lib.dexct_reduce_max(ptr(g1), int(dt == torch.float64), g1.numel(), ptr(gmax), stream_ptr()),
-                  'dexct_reduce_max')
+    gmax = _sino_max(lib, g1)
     a = torch.empty(tuple(g1.shape) + (2,), dtype=torch.float64, device=dev)
     bounds = [_shard.split(n_views, k, _PIPE_CHUNKS) for k in range(_PIPE_CHUNKS)]
     # where the results land: a block of host memory that is touched (a new one) and locked chunk by chunk while the pipeline
@@ -832,19 +872,16 @@ def _pipeline(lib, dev, a1, a2, i0, mus, n_iters, mask_thresh, precision, strict
         t1 = torch.empty((n_views, nC, nR), dtype=dt, device=dev)
         t2 = torch.empty_like(t1)
         eb = 4 if dt == torch.float32 else 8
-    global _last_ws, _last_events, _last_audit
-    _last_ws, _last_events, _last_audit = [], [], None
     for k, ((b, e), ev) in enumerate(zip(bounds, arrived)):
         main.wait_event(ev)
-        kw = dict(out=a[b:e], mask_max=gmax, mask_frac=float(mask_thresh), stop_tol=stop_tol, accumulate_stats=True,
-                  two_level=two_level, audit=audit, audit_strict=audit_strict)
+        kw = dict(solver, out=a[b:e], mask_max=gmax, mask_frac=float(mask_thresh), accumulate_stats=k > 0)
         if row_fastest:
             for src, dst in ((g1, t1), (g2, t2)):
                 _native.check(lib.dexct_transpose_batched(ptr(src[b:e]), ptr(dst[b:e]), e - b, nR, nC, eb, stream_ptr()),
                               'dexct_transpose_batched')
-            gn_device(t1[b:e], t2[b:e], i0, mus, n_iters, precision, out_rc=(nR, nC), **kw)
+            gn_device(t1[b:e], t2[b:e], i0, mus, n_iters, out_rc=(nR, nC), **kw)
         else:
-            gn_device(g1[b:e], g2[b:e], i0, mus, n_iters, precision, **kw)
+            gn_device(g1[b:e], g2[b:e], i0, mus, n_iters, **kw)
         done = torch.cuda.Event()
         done.record(main)
         with torch.cuda.stream(down):
@@ -859,12 +896,7 @@ def _pipeline(lib, dev, a1, a2, i0, mus, n_iters, mask_thresh, precision, strict
     down.synchronize()
     out = lazy.finish() if lazy is not None else host.numpy()          # (every copy has landed)
     if strict:
-        bad = ~torch.isfinite(a).all(dim=-1)
-        n_bad = int(bad.sum().item())
-        if n_bad:
-            first = bad.flatten().nonzero()[:1].flatten().tolist()
-            raise SingularHessianError(f'Singular matrix: {n_bad} pixel(s) outside the air mask ended non-finite '
-                                       f'after {n_iters} Newton iterations (first flat index on this rank: {first})')
+        _raise_if_singular(a, n_iters)
     return out[..., 0], out[..., 1]
 
 
@@ -892,6 +924,7 @@ def get_basismat_sinos(ct, sino_raw_1, sino_raw_2, spec1, spec2, n_iters=30, mas
     lib = _native.load()
     dev = device()
     _, i0, mus = decomposition_tables(ct, spec1, spec2)
+    solver = dict(precision=precision, stop_tol=stop_tol, two_level=two_level, audit=audit, audit_strict=audit_strict)
     rank, world = _shard.world()
     n_views = getattr(ct, 'N_proj', None)
     full_in = world > 1 and n_views is not None and sino_raw_1.shape[0] == n_views
@@ -903,35 +936,18 @@ def get_basismat_sinos(ct, sino_raw_1, sino_raw_2, spec1, spec2, n_iters=30, mas
     if (world == 1 and not verbose and not isinstance(sino_raw_1, torch.Tensor) and np.ndim(sino_raw_1) >= 2
             and np.shape(sino_raw_1)[0] >= 2 * _PIPE_CHUNKS and np.size(sino_raw_1) >= _PIPE_MIN_PIXELS
             and np.shape(sino_raw_1) == np.shape(sino_raw_2)):
-        return _basismat_sinos_pipelined(lib, dev, sino_raw_1, sino_raw_2, i0, mus, n_iters, mask_thresh, precision, strict, stop_tol,
-                                         two_level, audit, audit_strict)
+        return _basismat_sinos_pipelined(lib, dev, sino_raw_1, sino_raw_2, i0, mus, n_iters, mask_thresh, strict, solver)
     g1 = _as_device_counts(sino_raw_1, dev)
     g2 = _as_device_counts(sino_raw_2, dev).to(g1.dtype)
-    is64 = int(g1.dtype == torch.float64)
-    gmax = torch.empty((), dtype=torch.float64, device=dev)
-    _native.check(lib.dexct_reduce_max(ptr(g1), is64, g1.numel(), ptr(gmax), stream_ptr()), 'dexct_reduce_max')
-    gmax = _shard.global_max(gmax)
+    gmax = _shard.global_max(_sino_max(lib, g1))
     # the mask is applied inside the kernel (threshold read from the device scalar: no host round trip)
     import time
     t0 = time.time()
-    a = gn_device(g1, g2, i0, mus, n_iters, precision, mask_max=gmax, mask_frac=float(mask_thresh), stop_tol=stop_tol,
-                  two_level=two_level, audit=audit, audit_strict=audit_strict)
+    a = gn_device(g1, g2, i0, mus, n_iters, mask_max=gmax, mask_frac=float(mask_thresh), **solver)
     if verbose and rank == 0 and g1.dim() >= 2:
-        done = torch.cuda.Event()
-        done.record()
-        _progress_lines(_last_ws[-1], int(g1.shape[0]), int(g1.numel() // max(int(g1.shape[0]), 1)), done, t0)
+        _progress_lines(_last_run, int(g1.shape[0]), int(g1.numel() // max(int(g1.shape[0]), 1)), t0)
     if strict:
-        bad = ~torch.isfinite(a).all(dim=-1)          # masked pixels are exactly 0, hence finite
-        n_bad = int(bad.sum().item())
-        if world > 1:
-            t = torch.tensor(float(n_bad), dtype=torch.float64,
-                             device='cpu' if torch.distributed.get_backend() == 'gloo' else dev)
-            torch.distributed.all_reduce(t)            # every rank raises, or none
-            n_bad = int(t.item())
-        if n_bad:
-            first = bad.flatten().nonzero()[:1].flatten().tolist()
-            raise SingularHessianError(f'Singular matrix: {n_bad} pixel(s) outside the air mask ended non-finite '
-                                       f'after {n_iters} Newton iterations (first flat index on this rank: {first})')
+        _raise_if_singular(a, n_iters, world=world)
     if full_in:
         a = _shard.gather_views(a, n_views, view_dim=0, tag='get_basismat_sinos', mode=_shard.dropin_mode())     # a new tensor: the caller owns it
     if isinstance(sino_raw_1, torch.Tensor):
@@ -986,16 +1002,9 @@ def get_basismat_sinos_multi(ct, sinos, specs, materials=(matcomp1, matcomp2), n
     tensors_in = isinstance(sinos[0], torch.Tensor)
     first = _as_device_counts(sinos[0], dev)
     g = torch.stack([first] + [_as_device_counts(s, dev).to(first.dtype) for s in sinos[1:]])
-    gmax = torch.empty((), dtype=torch.float64, device=dev)
-    _native.check(lib.dexct_reduce_max(ptr(g[0]), int(g.dtype == torch.float64), g[0].numel(), ptr(gmax), stream_ptr()), 'dexct_reduce_max')
-    a = gn_device_multi(g, i0, mus, n_iters, mask_max=gmax, mask_frac=float(mask_thresh))
+    a = gn_device_multi(g, i0, mus, n_iters, mask_max=_sino_max(lib, g[0]), mask_frac=float(mask_thresh))
     if strict:
-        bad = ~torch.isfinite(a).all(dim=-1)          # masked pixels are exactly 0, hence finite
-        n_bad = int(bad.sum().item())
-        if n_bad:
-            first_bad = bad.flatten().nonzero()[:1].flatten().tolist()
-            raise SingularHessianError(f'Singular matrix: {n_bad} pixel(s) outside the air mask ended non-finite '
-                                       f'after {n_iters} Newton iterations (first flat index: {first_bad})')
+        _raise_if_singular(a, n_iters, where='')
     if not tensors_in:
         a = to_host(a)
     return tuple(a[..., m] for m in range(n_mats))

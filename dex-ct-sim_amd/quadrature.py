@@ -185,6 +185,7 @@ def max_rel_error(mu, w, cols, w_red, L):
 
 GATE_VERSION = 9           # part of the key of the on-disk copy of a gate table (matdecomp._gate_cache_path): bump with any change here
 START_HEADER = 12          # doubles before the tables (csrc/gn.hip, gn_start)
+POWER_CELL = 6 * 6 * 2     # doubles per cell of the power form behind the parts of start_layout: 6 x 6 coefficient pairs (kPowerCell)
 GATE_CELLS = 384           # cells per axis of the grid over (ln u0, u1 / u0).  The error of the kernel's 6 x 6 Lagrange interpolant of the fixed
                            # points goes with the sixth power of the cell size, and it is NOT uniform over the plane: at 256 cells (round 5)
                            # 2e-11 of |a| at the median point but 1.4e-9 at the median WATER ray - water in a tissue / bone basis sits at the edge

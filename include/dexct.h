@@ -422,7 +422,7 @@ int dexct_download(void* host, const void* device_src, int64_t n_bytes, void* st
  *               even when `start` carries a reduced residual rule (below).
  *   blocks_per_cu   > 0: workgroups per CU of the queue kernels (0: what is resident; results do not depend on it).
  * THE REDUCED RESIDUAL RULE (optional).  [10] = 3 instead of 2 says that, behind the power form of the interpolant ([11]: its
- * offset o, 72 n^2 doubles long), the array carries a block made by dexct_gn_reduced_rows: the one-step launch then sums the
+ * offset o, 6 x 6 pairs = 72 doubles per cell, n^2 cells), the array carries a block made by dexct_gn_reduced_rows: the one-step launch then sums the
  * residual of its chord step over the block's rows instead of the full tables.  A start array with [10] = 2 runs as before. */
 #define DEXCT_GN_DEFAULT_STOP_TOL 1e-12
 #define DEXCT_GN_PASS_COUNT 1
@@ -464,13 +464,13 @@ typedef struct dexct_gn_options {
  *   options    see dexct_gn_options; NULL = defaults
  *   workspace  device scratch of dexct_gn_workspace_bytes(n_energies, n_bins) bytes (the product tables
  *              the kernel reads through the scalar cache); owned by the caller, no hidden state.  After the call
- *              the uint64 at byte offset 72 holds, as a diagnostic, the number of pixel-iterations the float64
+ *              the uint64 at byte offset DEXCT_GN_WS_EXECUTED holds, as a diagnostic, the number of pixel-iterations the float64
  *              shared-spectrum kernels executed (what bench.py's executed-flop rate is computed from; 0 for the
- *              other kernels), and the uint64 at byte offset 80 the number of pixels handed to waves so far -
+ *              other kernels), and the uint64 at DEXCT_GN_WS_PROGRESS the number of pixels handed to waves so far -
  *              updated tile by tile WHILE the kernel runs, so a host thread may read it (on another stream) as a progress
- *              indicator: the reference prints a line every 20 views, matdecomp.py:111-112.  The uint64 at byte offset 88
- *              is the head of the tile queue, the one at 96 counts lane-steps that had to wait for a free result slot
- *              (diagnostic); the library zeroes all four words at the start of every call
+ *              indicator: the reference prints a line every 20 views, matdecomp.py:111-112.  The uint64 at DEXCT_GN_WS_QUEUE_HEAD
+ *              is the head of the tile queue, the one at DEXCT_GN_WS_STALLS counts lane-steps that had to wait for a free result
+ *              slot (diagnostic); the library zeroes all four words at the start of every call
  * n_iters is the reference's iteration count.  The update is a pure function of the two doubles, so the
  * kernel stops a pixel at the first state that repeats bit for bit (fixed point or cycle of up to 9 states) and
  * returns the state the cycle holds at iteration n_iters: the result of all n_iters iterations, exactly; with a tolerance
@@ -480,9 +480,14 @@ typedef struct dexct_gn_options {
  * a number >= 0 is ignored); DEXCT_GN_FULL_LOOP=1 = DEXCT_GN_FLAG_FULL_LOOP on every call; DEXCT_GN_BLOCKS_PER_CU=<n> = the
  * default of options->blocks_per_cu; DEXCT_GN_COOP_BELOW=<pixels> moves the size below which the cooperative kernel runs;
  * DEXCT_GN_SORT=0 = DEXCT_GN_FLAG_NATURAL_ORDER on every call; DEXCT_GN_TILES_PER_FETCH=<n> queue positions a wave reserves per
- * atomic; DEXCT_GN_REDUCED=0 = DEXCT_GN_FLAG_FULL_RESIDUAL on every call.  The uint64 at byte offset 104 of the workspace holds,
- * after a DEXCT_GN_FLAG_ONE_STEP launch, the number of table rows the chord residual summed per pixel (n_energies: the full
+ * atomic; DEXCT_GN_REDUCED=0 = DEXCT_GN_FLAG_FULL_RESIDUAL on every call.  The uint64 at DEXCT_GN_WS_RESIDUAL_ROWS of the workspace
+ * holds, after a DEXCT_GN_FLAG_ONE_STEP launch, the number of table rows the chord residual summed per pixel (n_energies: the full
  * tables). */
+#define DEXCT_GN_WS_EXECUTED 72        /* byte offsets of the workspace's diagnostic uint64 words */
+#define DEXCT_GN_WS_PROGRESS 80
+#define DEXCT_GN_WS_QUEUE_HEAD 88
+#define DEXCT_GN_WS_STALLS 96
+#define DEXCT_GN_WS_RESIDUAL_ROWS 104
 int64_t dexct_gn_workspace_bytes(int32_t n_energies, int32_t n_bins);
 int dexct_gn_decompose(const void* g1, const void* g2, int32_t g_is_f64, int64_t n_pix, const double* i0,
                        const double* mus, int32_t n_energies, int32_t n_bins, int32_t bin_div, int32_t n_iters,

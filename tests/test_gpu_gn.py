@@ -1063,6 +1063,33 @@ def test_sampled_audit_of_the_short_cut(hip, golden, recwarn):
     assert torch.equal(ok.view(torch.int64), exact.view(torch.int64))            # 5 steps: nothing takes the short cut
 
 
+def test_run_record_of_an_audited_and_an_accumulated_call(hip, golden):
+    """last_gn_stats() describes the caller's launches only: an audit of EVERY pixel (its exact re-solve is a launch of its own)
+    leaves mode, launch count and executed steps what they are without it and adds its own entry; accumulate_stats appends a
+    second launch to the same record.  7 x 37 pixels: four full tiles and an edge tile of three."""
+    from dex_ct_sim_amd import matdecomp as md
+    rng = np.random.default_rng(2031)
+    i0, mus = golden['gn0_i0'], golden['gn0_mus']
+    a_true = np.stack([rng.uniform(0.5, 30.0, 259), rng.uniform(0.0, 6.0, 259)], -1)
+    g = torch.tensor(np.stack([(i0[k] * np.exp(-a_true @ mus)).sum(-1) for k in range(2)]).reshape(2, 7, 37), device='cuda')
+    walked = md.gn_device(g[0], g[1], i0, mus, 50, two_level=False, audit=0)
+    n_walked = md.last_gn_stats()['pixel_iterations']
+    plain = md.gn_device(g[0], g[1], i0, mus, 50, audit=0)
+    st_plain = md.last_gn_stats()
+    audited = md.gn_device(g[0], g[1], i0, mus, 50, audit=1e6)
+    st = md.last_gn_stats()
+    print(st_plain, st, n_walked)
+    assert st['mode'] in md.SHORTCUT_MODES and st['launches'] == 1
+    assert st['pixel_iterations'] == st_plain['pixel_iterations'] > 0 and 'audit' not in st_plain
+    assert st['audit']['pixels'] == 259
+    assert {k: v for k, v in st.items() if k not in ('audit', 'main_ms')} == {k: v for k, v in st_plain.items() if k != 'main_ms'}
+    assert torch.equal(audited.view(torch.int64), plain.view(torch.int64))
+    again = md.gn_device(g[0], g[1], i0, mus, 50, two_level=False, audit=0, accumulate_stats=True)
+    st2 = md.last_gn_stats()
+    assert st2['launches'] == 2 and st2['pixel_iterations'] == st['pixel_iterations'] + n_walked and n_walked > st['pixel_iterations']
+    assert st2['mode'] == 'single' and st2['audit'] == st['audit'] and torch.equal(again.view(torch.int64), walked.view(torch.int64))
+
+
 def test_gate_table_survives_the_process_on_disk(hip, golden, tmp_path, monkeypatch):
     """The reference's usage is one call per pair of spectra per run (main.py:153): the gate's table is kept under
     DEXCT_CACHE_DIR and a fresh process (here: a cleared in-process cache) loads it instead of calibrating - same table, same

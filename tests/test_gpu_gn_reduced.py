@@ -80,7 +80,7 @@ def plane(hip, request):
     _, c0, k0, _ = quadrature.start_layout(n)
     with_rule = gate['start']
     assert with_rule[10].item() == 3.0
-    off = int(with_rule[11].item()) + 72 * n * n
+    off = int(with_rule[11].item()) + quadrature.POWER_CELL * n * n
     block = with_rule[off:].cpu().numpy()
     assert int(block[0]) == info['nodes'] == len(gate['rule']['nodes']) and block.size == int(block[9]) == 16 + 14 * info['nodes']
     assert int(block[1] + block[3] + block[5]) == info['nodes']

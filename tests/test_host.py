@@ -333,6 +333,81 @@ def test_default_tolerance_is_resolved_once_by_one_parser(monkeypatch):
     assert md._default_stop_tol() == 0.0
 
 
+def test_shared_layout_words_have_one_name_each():
+    """The workspace's diagnostic words and the power form's cell size are shared by the header, the kernels and the Python
+    host: the DEXCT_GN_WS_* macros of include/dexct.h equal their _native mirrors and the published offsets, and the power-cell
+    number places the reduced rule's block where start_layout-style arithmetic says."""
+    import torch
+    from dex_ct_sim_amd import _native, matdecomp as md, quadrature
+    hdr = open(os.path.join(ROOT, 'include', 'dexct.h')).read()
+    macros = {k: int(v) for k, v in re.findall(r'^#define DEXCT_GN_WS_([A-Z_]+) (\d+)\b', hdr, re.M)}
+    assert macros == {'EXECUTED': 72, 'PROGRESS': 80, 'QUEUE_HEAD': 88, 'STALLS': 96, 'RESIDUAL_ROWS': 104}
+    for name, value in macros.items():
+        assert getattr(_native, 'GN_WS_' + name) == value, name
+    assert _native.GN_WS_WORDS == slice(72, 112)
+    assert quadrature.POWER_CELL == 72
+    # a start array with n = 5 cells per axis, its power form right behind the tables: reduced_block insists that the array ends
+    # 72 n^2 doubles after the offset in word [11]
+    n = 5
+    end = quadrature.start_layout(n)[-1]
+    assert end == quadrature.START_HEADER + 2 * (n + 1) ** 2 + 4 * n * n
+    off = end + (end & 1)
+    start = torch.zeros(off + 72 * n * n, dtype=torch.float64)
+    start[3], start[10], start[11] = float(n), 2.0, float(off)
+    with pytest.raises(ValueError, match='ends with its power form'):
+        md.reduced_block(start[:-1], None, None)
+    with pytest.raises(ValueError, match='ends with its power form'):
+        md.reduced_block(torch.cat([start, torch.zeros(1, dtype=torch.float64)]), None, None)
+    mus = np.array([[0.2, 0.3, 0.25], [0.5, 0.1, 0.3]])
+    out = md.reduced_block(start, {'nodes': np.array([0, 2], dtype=np.int32), 'w': np.ones((2, 2))}, mus)
+    assert out[10].item() == 3.0 and torch.equal(out[:off + 72 * n * n][11:], start[11:])
+    assert out.numel() == off + 72 * n * n + _native.GN_REDUCED_HEADER + 2 * _native.GN_TABLE_ROW and int(out[off + 72 * n * n]) == 2
+
+
+def test_gn_stats_are_a_pure_function_of_the_run_record():
+    """matdecomp._gn_stats on a record of two (CPU) workspaces with known words and no events: executed iterations and stalls
+    summed over the launches, the residual's rows the maximum in mode 'one' and the tables' n_e otherwise; no 'main_ms' without
+    events, no 'audit' without an audit; None before any call."""
+    import torch
+    from dex_ct_sim_amd import matdecomp as md
+    assert md._gn_stats(None) is None and md._gn_stats(md._GnRun()) is None
+
+    def workspace(executed, progress, head, stalls, rows):
+        ws = torch.full((160,), 0xA5, dtype=torch.uint8)
+        ws[72:112] = torch.tensor([executed, progress, head, stalls, rows], dtype=torch.int64).view(torch.uint8)
+        return ws
+
+    run = md._GnRun()
+    run.workspaces += [workspace(1000, 11, 12, 7, 48), workspace(2 ** 33 + 5, 13, 14, 0, 31)]
+    run.mode, run.n_energies = 'one', 140
+    assert md._gn_stats(run) == {'pixel_iterations': 2 ** 33 + 1005, 'stalled_lane_steps': 7, 'launches': 2, 'mode': 'one',
+                                 'residual_energies': 48}
+    run.mode = 'single'
+    assert md._gn_stats(run) == {'pixel_iterations': 2 ** 33 + 1005, 'stalled_lane_steps': 7, 'launches': 2, 'mode': 'single',
+                                 'residual_energies': 140}
+    run.audit = {'pixels': 3}
+    assert md._gn_stats(run)['audit'] == {'pixels': 3}
+
+
+def test_raise_if_singular_keeps_both_messages():
+    """strict=True of get_basismat_sinos / get_basismat_sinos_multi: silent on a finite result, else SingularHessianError (a
+    numpy.linalg.LinAlgError) with the count and the first flat pixel index - "on this rank" on the 2 x 2 paths only."""
+    import torch
+    from dex_ct_sim_amd import matdecomp as md
+    a = torch.zeros(3, 4, 2, dtype=torch.float64)
+    assert md._raise_if_singular(a, 30) is None and md._raise_if_singular(a, 30, where='') is None
+    a[1, 2, 0], a[2, 3, 1], a[2, 0, 0] = float('nan'), float('inf'), float('-inf')
+    assert issubclass(md.SingularHessianError, np.linalg.LinAlgError)
+    with pytest.raises(md.SingularHessianError) as e:
+        md._raise_if_singular(a, 30)
+    assert str(e.value) == ('Singular matrix: 3 pixel(s) outside the air mask ended non-finite after 30 Newton iterations '
+                            '(first flat index on this rank: [6])')
+    with pytest.raises(np.linalg.LinAlgError) as e:
+        md._raise_if_singular(a[2:], 7, where='')
+    assert str(e.value) == ('Singular matrix: 2 pixel(s) outside the air mask ended non-finite after 7 Newton iterations '
+                            '(first flat index: [0])')
+
+
 def test_gate_table_on_disk_is_validated_before_use(tmp_path, monkeypatch):
     """The gate of the Newton short cut is kept under DEXCT_CACHE_DIR between processes (matdecomp._gate_to_disk /
     _gate_from_disk): a complete file for the same tables, tolerance and library is taken; a truncated, edited or foreign one
