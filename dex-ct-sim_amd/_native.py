@@ -16,8 +16,11 @@ SYMBOLS = ['dexct_strerror', 'dexct_abi_version', 'dexct_last_hip_error', 'dexct
            'dexct_siddon_project_grouped_packed', 'dexct_poisson_detect', 'dexct_vmi', 'dexct_label_moments', 'dexct_fdk_backproject', 'dexct_sino_allgather', 'dexct_sino_gather', 'dexct_transpose_log', 'dexct_host_pin', 'dexct_host_touch', 'dexct_host_unpin', 'dexct_download',
            'dexct_volume_ids', 'dexct_volume_remap', 'dexct_fbp_parker', 'dexct_sino_log', 'dexct_cone_layout_groups', 'dexct_cone_project_grouped',
            'dexct_bhc_linearize', 'dexct_image_project', 'dexct_image_backproject', 'dexct_sirt_residual', 'dexct_sirt_update',
-           'dexct_gn_reduced_rows', 'dexct_gn_decompose_multi', 'dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes',
-           'dexct_gn_multi_workspace_bytes']
+           'dexct_gn_reduced_rows', 'dexct_gn_decompose_multi', 'dexct_gn_covariance', 'dexct_cov_quadform',
+           'dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes', 'dexct_gn_multi_workspace_bytes', 'dexct_gn_cov_workspace_bytes']
+# the size queries return int64_t; dexct_strerror a string; every other entry point an int status
+SIZE_QUERIES = ['dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes', 'dexct_gn_multi_workspace_bytes',
+                'dexct_gn_cov_workspace_bytes']
 
 
 class FanGeom(C.Structure):
@@ -70,6 +73,7 @@ GN_WS_WORDS = slice(GN_WS_EXECUTED, GN_WS_RESIDUAL_ROWS + 8)   # ... of the work
 GN_TABLE_ROW = 14        # doubles per energy row of the Newton tables (csrc/gn.hip, kTab)
 GN_MAX_MEAS, GN_MAX_MATS = 4, 3   # DEXCT_GN_MAX_MEAS, DEXCT_GN_MAX_MATS (dexct_gn_decompose_multi)
 GN_MULTI_FULL_LOOP = 1   # DEXCT_GN_MULTI_FULL_LOOP
+COV_ESTIMATOR, COV_CRLB = 0, 1   # DEXCT_COV_* (dexct_gn_covariance)
 
 
 def gn_options(stop_tol=None, out_rows=0, out_channels=0, kernel=0, gn_pass=0, iterations=None, start=None, flags=0,
@@ -166,7 +170,6 @@ def load():
     lib.dexct_cone_project_grouped.argtypes = [C.POINTER(FanGeom), vp, vp, vp, vp, f64, f64, i32, i32, vp, i32, i32, i32, vp, vp, vp,
                                                vp, vp, vp, vp, vp, vp, vp]
     lib.dexct_cone_layout_bytes.argtypes = [i32, i32, i32]
-    lib.dexct_cone_layout_bytes.restype = i64
     lib.dexct_siddon_project_grouped.argtypes = [C.POINTER(FanGeom), vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp,
                                                  i32, vp, vp, vp, vp, vp]
     lib.dexct_siddon_project_grouped_packed.argtypes = lib.dexct_siddon_project_grouped.argtypes
@@ -178,16 +181,17 @@ def load():
     lib.dexct_siddon_trace.argtypes = [C.POINTER(FanGeom), vp, vp, i32, i32, vp, vp, vp, vp]
     lib.dexct_gn_decompose.argtypes = [vp, vp, i32, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp, f64, vp, C.POINTER(GnOptions), vp, vp]
     lib.dexct_gn_workspace_bytes.argtypes = [i32, i32]
-    lib.dexct_gn_workspace_bytes.restype = i64
     lib.dexct_gn_apply_mask.argtypes = [vp, i32, i64, f64, vp, vp]
     lib.dexct_gn_model_sums.argtypes = [vp, i64, vp, vp, i32, vp, vp, vp, vp]
     lib.dexct_reduce_max.argtypes = [vp, i32, i64, vp, vp]
     lib.dexct_gn_reduced_rows.argtypes = [vp, i32, vp, i32, vp, vp, vp, i64]
     lib.dexct_gn_decompose_multi.argtypes = [vp, i32, i64, i32, i32, vp, vp, i32, i32, vp, f64, i32, vp, vp, vp]
     lib.dexct_gn_multi_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.dexct_gn_multi_workspace_bytes.restype = i64
-    for name in SYMBOLS[3:-3]:
-        getattr(lib, name).restype = C.c_int
+    lib.dexct_gn_covariance.argtypes = [vp, i64, i32, i32, vp, vp, vp, i32, i32, vp, i32, vp, f64, vp, vp, vp]
+    lib.dexct_cov_quadform.argtypes = [vp, i64, i32, vp, vp, vp]
+    lib.dexct_gn_cov_workspace_bytes.argtypes = [i32, i32, i32]
+    for name in SYMBOLS[1:]:
+        getattr(lib, name).restype = i64 if name in SIZE_QUERIES else C.c_int
     _lib = lib
     return lib
 

@@ -11,6 +11,9 @@ for every run in the parameter file, for every dual-energy spectrum pair:
      beam-hardening-corrected images of every log sinogram, ``recon_{water,bone}BHC_{raw,HU}_float32.bin`` (the files
      the reference's plots.py:184-195 reads; basis-material sinograms are linear in thickness already and get none);
      ``--recon sirt`` reconstructs all of them iteratively (SIRT / OS-SART, iterative.py) instead of by FBP.
+  4. with ``--covariance``: the predicted noise covariance of the two basis-material sinograms per detector pixel
+     (matdecomp.get_basismat_covariance at the decomposed line integrals, for the doses of the pair), written next to them as
+     ``cov11_sino_float32.bin``, ``cov12_sino_float32.bin``, ``cov22_sino_float32.bin``; air pixels hold 0 like the sinograms.
 
 Differences from the reference script, all on purpose: inputs are command-line options instead of
 edited source lines (:80-82, :101-103); figures are off unless --show; both spectra of a pair are
@@ -31,7 +34,7 @@ sys.path.insert(0, os.path.dirname(HERE))
 import dex_ct_sim_amd as dx  # noqa: E402
 from dex_ct_sim_amd.back_project import get_recon  # noqa: E402
 from dex_ct_sim_amd.forward_project import get_sinos  # noqa: E402
-from dex_ct_sim_amd.matdecomp import get_basismat_sinos  # noqa: E402
+from dex_ct_sim_amd.matdecomp import get_basismat_covariance, get_basismat_sinos  # noqa: E402
 
 
 def load_spectrum(ct, spec_id, dose, input_dir):
@@ -90,7 +93,13 @@ def main(argv=None):
                          'pair, started from the FBP image; the output file names stay the reference\'s')
     ap.add_argument('--recon-iters', type=int, default=20, help='iterations of --recon sirt')
     ap.add_argument('--recon-subsets', type=int, default=1, help='ordered subsets of --recon sirt (1: SIRT, more: OS-SART)')
+    ap.add_argument('--covariance', nargs='?', const='estimator', default=None, choices=['estimator', 'crlb'],
+                    help='also write the predicted noise covariance of each decomposed pair (cov11 / cov12 / cov22 _sino_float32.bin '
+                         'beside mat1_sino): of what the Newton solve returns (estimator, the default) or the Cramer-Rao bound '
+                         '(crlb); single process only')
     args = ap.parse_args(argv)
+    if args.covariance and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        ap.error('--covariance runs on a single process')
     recon_kw = {} if args.recon == 'fbp' else dict(method=args.recon, n_iters=args.recon_iters, n_subsets=args.recon_subsets)
 
     import torch.distributed as dist
@@ -154,6 +163,11 @@ def main(argv=None):
                 matsino2.astype(np.float32).tofile(sub_dir + 'mat2_sino_float32.bin')
                 if args.show:
                     show('Basis material 1', matsino1, 'Basis material 2', matsino2)
+                if args.covariance:
+                    print(f'Predicting the noise covariance of the basis material sinograms ({args.covariance})!')
+                    cov = get_basismat_covariance(ct, (matsino1, matsino2), specs, kind=args.covariance, mask_from=sinos[0][0])
+                    for t, name in enumerate(('cov11', 'cov12', 'cov22')):
+                        cov[..., t].astype(np.float32).tofile(sub_dir + f'{name}_sino_float32.bin')
                 if do_bp:
                     print('Back projecting basis material sinograms!')
                     for i, matsino in enumerate([matsino1, matsino2]):

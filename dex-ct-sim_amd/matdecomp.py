@@ -956,11 +956,13 @@ def get_basismat_sinos(ct, sino_raw_1, sino_raw_2, spec1, spec2, n_iters=30, mas
     return a[..., 0], a[..., 1]
 
 
-def decomposition_tables_multi(ct, specs, materials=(matcomp1, matcomp2)):
+def decomposition_tables_multi(ct, specs, materials=(matcomp1, matcomp2), with_variance=False):
     """matdecomp.py:140-160 for any number of spectra and basis materials: (ee, i0 [K, nE], mus [M, nE]) - the union energy
     grid of all spectra, dE with the first bin from 0, the detector response (times E for an energy-integrating detector),
     np.interp of each spectrum, xcompy.mixatten of each material.  With two spectra and the default materials this is
-    decomposition_tables."""
+    decomposition_tables.  ``with_variance`` appends i0v [K, nE], the weights of the variance of the detected signal: i0 x E
+    for an energy-integrating detector, i0 for a counting one (the w2 of forward_project.merged_tables) - meaningful for spectra
+    scaled to photons."""
     specs = list(specs)
     if not specs:
         raise ValueError('at least one spectrum is needed')
@@ -971,6 +973,8 @@ def decomposition_tables_multi(ct, specs, materials=(matcomp1, matcomp2)):
         detresponse = detresponse * ee
     i0 = np.stack([np.interp(ee, sp.E, sp.I0) * detresponse * dE for sp in specs])
     mus = np.stack([xc.mixatten(m, ee) for m in materials])
+    if with_variance:
+        return ee, i0, mus, i0 * (ee if ct.eid else 1.0)
     return ee, i0, mus
 
 
@@ -1008,3 +1012,98 @@ def get_basismat_sinos_multi(ct, sinos, specs, materials=(matcomp1, matcomp2), n
     if not tensors_in:
         a = to_host(a)
     return tuple(a[..., m] for m in range(n_mats))
+
+
+# ---- the noise covariance of the decomposed line integrals (csrc/gn_cov.hip, dexct_gn_covariance) -----------------------------
+COV_KINDS = {'estimator': _native.COV_ESTIMATOR, 'crlb': _native.COV_CRLB}
+
+
+def _cov_kind(kind):
+    if kind not in COV_KINDS:
+        raise ValueError(f'kind={kind!r}: the covariance is one of {sorted(COV_KINDS)}')
+    return COV_KINDS[kind]
+
+
+def gn_covariance_device(a, i0, i0v, mus, kind='estimator', mask_g=None, mask_max=None, mask_frac=0.95, out=None):
+    """The covariance of the decomposed line integrals at the states ``a`` (dexct_gn_covariance): a device tensor [..., M]
+    (float64), i0 / i0v [K, nE] and mus [M, nE] host arrays or device tensors.  ``kind``: 'estimator' - the delta-method
+    covariance of the Poisson-likelihood Newton solve - or 'crlb'.  ``mask_g`` (device tensor of a's pixel shape, float32 or
+    float64: the counts of measurement 0) with ``mask_max`` (device float64 scalar): pixels with mask_g >= mask_frac * max get
+    exact zeros.  Returns a device tensor [..., T] float64, T = M (M + 1) / 2: the row-major upper triangle."""
+    kind_id = _cov_kind(kind)
+    if not isinstance(a, torch.Tensor) or a.dim() < 1:
+        raise ValueError('a must be a device tensor [..., nMats]')
+    shp = lambda x: tuple(x.shape) if hasattr(x, 'shape') else np.shape(x)
+    n_mats = int(a.shape[-1])
+    if shp(mus)[:1] != (n_mats,):
+        raise ValueError(f'a holds {n_mats} line integrals per pixel but mus has shape {shp(mus)}')
+    n_meas, n_mats, n_e = _check_multi_shapes(int(shp(i0)[0]) if len(shp(i0)) else 0, shp(i0), shp(mus), 1)
+    if shp(i0v) != shp(i0):
+        raise ValueError(f'i0v must have the shape of i0 {shp(i0)}, got {shp(i0v)}')
+    shape = tuple(a.shape[:-1])
+    n_pix = int(np.prod(shape))
+    n_tri = n_mats * (n_mats + 1) // 2
+    if (mask_g is None) != (mask_max is None):
+        raise ValueError('mask_g and mask_max go together')
+    if mask_g is not None and (not isinstance(mask_g, torch.Tensor) or tuple(mask_g.shape) != shape):
+        raise ValueError(f'mask_g must be a device tensor of shape {shape}')
+    if out is not None and (out.numel() != n_tri * n_pix or out.dtype != torch.float64 or not out.is_contiguous()):
+        raise ValueError(f'out must be a contiguous float64 tensor with {n_tri} values per pixel')
+    for name, t in (('a', a), ('mask_g', mask_g), ('mask_max', mask_max), ('out', out)):
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != a.device):
+            raise ValueError(f'{name} must be a tensor on the device of a, and that a GPU (got {getattr(t, "device", type(t).__name__)})')
+    lib = _native.load()
+    dev = a.device
+    a = a.to(torch.float64).contiguous()
+    if mask_g is not None:
+        if mask_g.dtype not in (torch.float32, torch.float64):
+            mask_g = mask_g.to(torch.float64)
+        mask_g = mask_g.contiguous()
+    tab = [to_dev(x if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64), torch.float64, dev) for x in (i0, i0v, mus)]
+    cov = out if out is not None else torch.empty(shape + (n_tri,), dtype=torch.float64, device=dev)
+    if n_pix == 0:
+        return cov
+    ws = torch.empty(lib.dexct_gn_cov_workspace_bytes(n_meas, n_mats, n_e), dtype=torch.uint8, device=dev)
+    _native.check(lib.dexct_gn_covariance(ptr(a), n_pix, n_meas, n_mats, ptr(tab[0]), ptr(tab[1]), ptr(tab[2]), n_e, kind_id,
+                                          ptr(mask_g), int(mask_g is not None and mask_g.dtype == torch.float64), ptr(mask_max),
+                                          float(mask_frac), ptr(cov), ptr(ws), stream_ptr()), 'dexct_gn_covariance')
+    return cov
+
+
+def get_basismat_covariance(ct, basis_sinos, specs, materials=(matcomp1, matcomp2), kind='estimator', mask_from=None,
+                            mask_thresh=0.95):
+    """The predicted noise covariance of basis-material sinograms: ``basis_sinos`` is the tuple get_basismat_sinos or
+    get_basismat_sinos_multi returned (M sinograms of one shape; a noise-free decomposition gives the covariance at the truth),
+    ``specs`` the K spectra they were decomposed from, scaled to photons as for a noisy scan.  ``kind``: 'estimator' (what the
+    Newton solve of this library returns) or 'crlb' (the Cramer-Rao bound).  ``mask_from``: the raw sinogram of specs[0]; its
+    air pixels (``>= mask_thresh * max``, the rule of get_basismat_sinos) get zeros.  Returns an array of the sinograms' shape
+    + (T,), T = M (M + 1) / 2, the row-major upper triangle (00, 01, 11) or (00, 01, 02, 11, 12, 22), float64.  NumPy in ->
+    NumPy out; device tensors in -> a device tensor out.  Single process only."""
+    _cov_kind(kind)
+    basis_sinos, specs, materials = list(basis_sinos), list(specs), list(materials)
+    n_meas, n_mats = len(specs), len(materials)
+    if len(basis_sinos) != n_mats:
+        raise ValueError(f'{len(basis_sinos)} basis sinograms for {n_mats} materials')
+    shapes = {tuple(np.shape(s)) for s in basis_sinos}
+    if len(shapes) != 1:
+        raise ValueError(f'the basis sinograms must agree in shape, got {sorted(shapes)}')
+    if not 2 <= n_meas <= GN_MAX_MEAS:
+        raise ValueError(f'{n_meas} spectra: the decomposition takes 2 to {GN_MAX_MEAS} measurements')
+    if not 2 <= n_mats <= min(GN_MAX_MATS, n_meas):
+        raise ValueError(f'{n_mats} basis materials: the decomposition takes 2 to {GN_MAX_MATS}, and no more than measurements')
+    if mask_from is not None and tuple(np.shape(mask_from)) != next(iter(shapes)):
+        raise ValueError(f'mask_from has shape {tuple(np.shape(mask_from))}, the basis sinograms {next(iter(shapes))}')
+    if _shard.world()[1] > 1:
+        raise NotImplementedError('get_basismat_covariance runs on a single process; shard the views by hand under torch.distributed')
+    _, i0, mus, i0v = decomposition_tables_multi(ct, specs, materials, with_variance=True)
+    lib = _native.load()
+    dev = device()
+    tensors_in = isinstance(basis_sinos[0], torch.Tensor)
+    a = torch.stack([s.to(dev).to(torch.float64) if isinstance(s, torch.Tensor)
+                     else to_dev(np.ascontiguousarray(s, dtype=np.float64), torch.float64, dev) for s in basis_sinos], dim=-1)
+    mask_g = mask_max = None
+    if mask_from is not None:
+        mask_g = _as_device_counts(mask_from, dev)
+        mask_max = _sino_max(lib, mask_g)
+    cov = gn_covariance_device(a, i0, i0v, mus, kind, mask_g=mask_g, mask_max=mask_max, mask_frac=float(mask_thresh))
+    return cov if tensors_in else to_host(cov)

@@ -16,6 +16,11 @@ and two sweeps the reference writes as Python loops over energies (one make_vmi 
   vmi_roi_sweep(Evals, M1, M2, roi_signal, roi_background)  ->  signal, noise, CNR per energy  (plots.py:386-395)
   vmi_rmse_sweep(Evals, M1, M2, gt_labels, gt_values, mask) ->  RMSE per energy                (plots.py:297-303)
 
+and the predicted noise of VMI sinograms from the covariance of the decomposition (matdecomp.get_basismat_covariance):
+
+  vmi_variance(cov, E, materials)        ->  variance sinogram of the VMI line integral at E   (HIP: dexct_cov_quadform)
+  vmi_noise_sweep(Evals, cov, materials) ->  mean predicted variance per energy, and the energy of least noise
+
 A VMI is ``u1(E) M1 + u2(E) M2``; mean, variance and squared error against a piecewise-constant ground truth
 are therefore closed forms in the second-order moments of (M1, M2) per region, which one pass of
 ``dexct_label_moments`` delivers for all energies at once (float64 sums of the float32 images; the reference
@@ -190,3 +195,64 @@ def vmi_rmse_sweep(Evals, M1, M2, gt_labels, gt_values, mask=None, HU=True, matc
     n = mom[:, 0].sum()
     rmse = np.sqrt(np.maximum(sse, 0.0) / n) if n > 0 else np.full(u1.shape, np.nan)
     return rmse * (1000.0 / uw) if HU else rmse
+
+
+def _basis_vector(E, materials):
+    from . import matdecomp as md
+    materials = (md.matcomp1, md.matcomp2) if materials is None else tuple(materials)
+    E = np.atleast_1d(np.asarray(E, dtype=np.float64))
+    return np.stack([xcompy.mixatten(m, E) for m in materials]), E        # [M, nE]
+
+
+def _check_cov(cov, n_mats):
+    n_tri = n_mats * (n_mats + 1) // 2
+    if n_mats not in (2, 3):
+        raise ValueError(f'{n_mats} basis materials: a covariance holds 2 or 3')
+    if cov.ndim < 1 or cov.shape[-1] != n_tri:
+        raise ValueError(f'cov must be [..., {n_tri}] for {n_mats} basis materials (the packed upper triangle), got {tuple(cov.shape)}')
+
+
+def vmi_variance(cov, E, materials=None):
+    """Variance of the VMI line integral ``sum_m u_m(E) a_m`` per pixel: ``u^T C u`` with the mass attenuation u_m(E) of the
+    basis ``materials`` (default: matdecomp.matcomp1, matcomp2) and the packed covariance ``cov`` [..., T] of
+    matdecomp.get_basismat_covariance (dexct_cov_quadform).  NumPy in -> NumPy out, device tensor in -> device tensor out."""
+    u, E = _basis_vector(E, materials)
+    if E.size != 1:
+        raise ValueError('vmi_variance takes one energy; vmi_noise_sweep takes many')
+    tensor_in = isinstance(cov, torch.Tensor)
+    _check_cov(cov, u.shape[0])
+    lib = _native.load()
+    c = cov.to(device()).to(torch.float64).contiguous() if tensor_in else to_dev(np.ascontiguousarray(cov, dtype=np.float64),
+                                                                                 torch.float64, device())
+    out = torch.empty(c.shape[:-1], dtype=torch.float64, device=c.device)
+    uvec = np.ascontiguousarray(u[:, 0])
+    _native.check(lib.dexct_cov_quadform(ptr(c), out.numel(), u.shape[0], uvec.ctypes.data, ptr(out), stream_ptr()),
+                  'dexct_cov_quadform')
+    return out if tensor_in else out.cpu().numpy()
+
+
+def vmi_noise_sweep(Evals, cov, materials=None, mask=None):
+    """Mean predicted variance of the VMI line integrals at every energy of ``Evals``, and the energy where it is least:
+    (variance [nE], E_min).  The mean over pixels of u^T C_p u is u^T mean(C) u, so the covariance is averaged once (over the
+    pixels of the boolean ``mask``, default all - leave the air pixels out, whose covariance is 0) and every energy is a
+    quadratic form in T numbers.  ``cov``: NumPy array or device tensor [..., T]."""
+    u, E = _basis_vector(Evals, materials)
+    _check_cov(cov, u.shape[0])
+    n_tri = cov.shape[-1]
+    if isinstance(cov, torch.Tensor):
+        c = cov.reshape(-1, n_tri).to(torch.float64)
+        if mask is not None:
+            c = c[torch.as_tensor(np.asarray(mask, dtype=bool).reshape(-1), device=c.device)]
+        cbar = c.mean(dim=0).cpu().numpy()
+    else:
+        c = np.asarray(cov, dtype=np.float64).reshape(-1, n_tri)
+        if mask is not None:
+            c = c[np.asarray(mask, dtype=bool).reshape(-1)]
+        cbar = c.mean(axis=0)
+    var = np.zeros(E.size)
+    t = 0
+    for i in range(u.shape[0]):
+        for j in range(i, u.shape[0]):
+            var += (u[i] * u[i] if i == j else 2.0 * u[i] * u[j]) * cbar[t]
+            t += 1
+    return var, float(E[int(np.argmin(var))])

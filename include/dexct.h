@@ -528,6 +528,49 @@ int dexct_gn_decompose_multi(const void* g, int32_t g_is_f64, int64_t n_pix, int
                              const double* mask_max, double mask_frac, int32_t flags, double* out_a,
                              void* workspace, void* stream);
 
+/* The per-pixel noise covariance of the decomposed line integrals (csrc/gn_cov.hip).  Additive to ABI 6.
+ * For a pixel with state a[n_mats] (what the decomposition returned, or a noise-free truth), in float64, with the exponent
+ * clipped at +-700 as in the decomposition, t_e = exp(clip(-sum_m a_m mu_m[e])):
+ *   nu_k = sum_e i0[k][e] t_e              the expected counts of measurement k
+ *   v_k  = sum_e i0v[k][e] t_e             their variance
+ *   G_km = sum_e i0[k][e] mu[m][e] t_e     = -d nu_k / d a_m
+ * i0v are the variance weights: i0 x E for an energy-integrating detector, i0 for a counting one - the w2 of the noisy
+ * projection (dexct_add_noise's variance input) - so the spectra must be scaled to photons.
+ *   kind = DEXCT_COV_ESTIMATOR  C = H^-1 (G^T diag(v / nu^2) G) H^-1 with H = G^T diag(1 / nu) G: the delta-method covariance of
+ *                               what the Poisson-likelihood Newton solve (dexct_gn_decompose, dexct_gn_decompose_multi)
+ *                               returns for counts of mean nu and variance v
+ *   kind = DEXCT_COV_CRLB       C = (G^T diag(1 / v) G)^-1: the Cramer-Rao bound for Gaussian data with those variances
+ * The two coincide when n_meas = n_mats or i0v = i0.  The inverse is closed form (2 x 2, or the 3 x 3 adjugate); a singular or
+ * non-finite pixel keeps what IEEE arithmetic gives (inf / NaN), in that pixel only.  A pixel whose exponent is NaN at some
+ * weighted energy (a NaN component of the state, infinite components of opposite sign, an infinite one against mu = 0) gets NaN
+ * in every element, as NumPy's clip keeps a NaN; otherwise an infinite component acts through the clip.
+ *   a[n_mats*p + m]         the states (float64), 8-byte aligned: the out_a of the decomposition
+ *   i0, i0v [k*n_energies + e], mus [m*n_energies + e]   device float64
+ *   out_cov[T*p + t]        T = n_mats (n_mats + 1) / 2 values per pixel, the row-major upper triangle: (00, 01, 11) for two
+ *                           materials, (00, 01, 02, 11, 12, 22) for three; 8-byte aligned; every pixel's T values are written
+ *   mask_g, g_is_f64, mask_max, mask_frac   the air mask of dexct_gn_decompose_multi: mask_g[p] are the counts of measurement
+ *                           0 (float64 or float32, aligned to the element), a pixel with mask_g[p] >= mask_frac * *mask_max gets
+ *                           exact zeros and is not computed; mask_g = NULL: no mask (mask_max is then not read); mask_g without
+ *                           mask_max is DEXCT_EINVAL
+ *   workspace               device scratch of dexct_gn_cov_workspace_bytes(n_meas, n_mats, n_energies) bytes (0 for sizes outside
+ *                           the limits), 8-byte aligned: one row per energy that i0 or i0v weights - the scaled -mu_m, then per
+ *                           measurement i0_k, i0v_k, i0_k mu_m.  Written by the call before it is read; no hidden state
+ * Limits and errors as for dexct_gn_decompose_multi: 2 <= n_mats <= n_meas <= DEXCT_GN_MAX_MEAS, n_mats <= DEXCT_GN_MAX_MATS,
+ * 1 <= n_energies <= 4096, n_pix >= 0 (0: nothing is launched); DEXCT_EINVAL / DEXCT_ERANGE before the first launch otherwise.
+ * No allocation, no synchronisation, no environment variable. */
+#define DEXCT_COV_ESTIMATOR 0
+#define DEXCT_COV_CRLB 1
+int64_t dexct_gn_cov_workspace_bytes(int32_t n_meas, int32_t n_mats, int32_t n_energies);
+int dexct_gn_covariance(const double* a, int64_t n_pix, int32_t n_meas, int32_t n_mats, const double* i0, const double* i0v,
+                        const double* mus, int32_t n_energies, int32_t kind, const void* mask_g, int32_t g_is_f64,
+                        const double* mask_max, double mask_frac, double* out_cov, void* workspace, void* stream);
+
+/* out[p] = u^T C_p u for the packed covariances cov[T*p + t] of dexct_gn_covariance and a HOST vector u[n_mats]: the variance of
+ * the line integral sum_m u_m a_m, e.g. of a virtual monoenergetic sinogram with u_m = the mass attenuation of basis m at one
+ * energy.  Summed as sum_i u_i^2 C_ii + 2 sum_(i<j) u_i u_j C_ij in the order of the triangle.  cov, out: device float64, 8-byte
+ * aligned, out must not overlap cov; n_mats = 2 or 3; n_pix = 0 launches nothing. */
+int dexct_cov_quadform(const double* cov, int64_t n_pix, int32_t n_mats, const double* u, double* out, void* stream);
+
 /* The energy sums of the decomposition's forward model (matdecomp.py:116-121) at n_states states a [n][2] (device float64), for the
  * table assembly of the short cut (quadrature.py, assemble_start / validate_start; no counterpart in the reference): nu_out
  * [n][2] = sum_e i0[k][e] exp(clip(-(a0 mu0[e] + a1 mu1[e]), +-700)); g_out [n][2][2] = sum_e i0[k][e] mu[m][e] x the same

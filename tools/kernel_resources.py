@@ -44,7 +44,7 @@ def resources(src):
             row[key] = int(m.group(1)) if m else None
         res.append(row)
     for row, nm in zip(res, demangle([r['kernel'] for r in res])):
-        row['kernel'] = re.sub(r'^void dexct::', '', nm).split('(')[0]
+        row['kernel'] = re.sub(r'^(void )?dexct::', '', nm.replace('(anonymous namespace)::', '')).split('(')[0]
     return res
 
 
