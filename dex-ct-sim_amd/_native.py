@@ -17,6 +17,7 @@ SYMBOLS = ['dexct_strerror', 'dexct_abi_version', 'dexct_last_hip_error', 'dexct
            'dexct_volume_ids', 'dexct_volume_remap', 'dexct_fbp_parker', 'dexct_sino_log', 'dexct_cone_layout_groups', 'dexct_cone_project_grouped',
            'dexct_bhc_linearize', 'dexct_image_project', 'dexct_image_backproject', 'dexct_sirt_residual', 'dexct_sirt_update',
            'dexct_gn_reduced_rows', 'dexct_gn_decompose_multi', 'dexct_gn_covariance', 'dexct_cov_quadform',
+           'dexct_fbp_var_filter', 'dexct_fbp_var_backproject', 'dexct_fdk_var_backproject',
            'dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes', 'dexct_gn_multi_workspace_bytes', 'dexct_gn_cov_workspace_bytes']
 # the size queries return int64_t; dexct_strerror a string; every other entry point an int status
 SIZE_QUERIES = ['dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes', 'dexct_gn_multi_workspace_bytes',
@@ -73,6 +74,7 @@ GN_WS_WORDS = slice(GN_WS_EXECUTED, GN_WS_RESIDUAL_ROWS + 8)   # ... of the work
 GN_TABLE_ROW = 14        # doubles per energy row of the Newton tables (csrc/gn.hip, kTab)
 GN_MAX_MEAS, GN_MAX_MATS = 4, 3   # DEXCT_GN_MAX_MEAS, DEXCT_GN_MAX_MATS (dexct_gn_decompose_multi)
 GN_MULTI_FULL_LOOP = 1   # DEXCT_GN_MULTI_FULL_LOOP
+FBP_VAR_MAX_CHANNELS = 2730   # DEXCT_FBP_VAR_MAX_CHANNELS (dexct_fbp_var_filter)
 COV_ESTIMATOR, COV_CRLB = 0, 1   # DEXCT_COV_* (dexct_gn_covariance)
 
 
@@ -178,6 +180,10 @@ def load():
     lib.dexct_fbp_filter.argtypes = [vp, vp, vp, i64, i32, f64, vp, vp]
     lib.dexct_fbp_parker.argtypes = [vp, i32, i32, i32, f64, f64, i32, i32, vp, vp]
     lib.dexct_fbp_backproject.argtypes = [vp, vp, i32, i32, i32, f64, f64, f64, i32, f64, vp, vp]
+    lib.dexct_fbp_var_filter.argtypes = [vp, i32, i32, i32, i32, vp, vp, f64, f64, i32, i32, vp, vp, vp]
+    lib.dexct_fbp_var_backproject.argtypes = [vp, vp, vp, i32, i32, i32, i32, f64, f64, f64, i32, f64, vp, vp]
+    lib.dexct_fdk_var_backproject.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f64, f64, f64, f64, f64, f64, f64, i32, f64, i32,
+                                              f64, f64, vp, vp]
     lib.dexct_siddon_trace.argtypes = [C.POINTER(FanGeom), vp, vp, i32, i32, vp, vp, vp, vp]
     lib.dexct_gn_decompose.argtypes = [vp, vp, i32, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp, f64, vp, C.POINTER(GnOptions), vp, vp]
     lib.dexct_gn_workspace_bytes.argtypes = [i32, i32]

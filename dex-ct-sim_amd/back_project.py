@@ -203,6 +203,104 @@ def get_recon(sino, ct, spec, N_matrix, FOV, ramp, window=None, slices=None, bhc
     return raw, (1000.0 * (raw - mu_w) / mu_w).astype(np.float32)
 
 
+def _check_cov_sino(shape, ct, window):
+    """The host checks of a covariance sinogram [N_proj, (N_rows,) N_channels, T] against ``ct``: everything that can be
+    refused before the device is touched.  Returns the window's name."""
+    shape = tuple(shape)
+    if len(shape) == 2:
+        raise ValueError(f'covariance sinogram {shape} has no plane axis: pass a single variance sinogram as var[..., None]')
+    if len(shape) not in (3, 4):
+        raise ValueError(f'covariance sinogram must be [N_proj, N_channels, T] or [N_proj, N_rows, N_channels, T], got {shape}')
+    if shape[0] != ct.N_proj or shape[-2] != ct.N_channels:
+        raise ValueError(f'covariance sinogram {shape} does not match the scanner ({ct.N_proj} x {ct.N_channels})')
+    if shape[-1] < 1:
+        raise ValueError('covariance sinogram has no planes')
+    window = window or default_window()
+    if window not in WINDOWS:
+        raise ValueError(f'unknown filter window {window!r}; choose from {sorted(WINDOWS)}')
+    if ct.theta_tot > 2 * np.pi + 1e-4:
+        raise ValueError(f'rotation_angle_total = {ct.theta_tot:.6g} exceeds 2 pi: more than one rotation is not reconstructed')
+    if ct.theta_tot < 2 * np.pi - 1e-4:
+        need = np.pi + (ct.N_channels - 1) * ct.dgamma
+        if ct.theta_tot < need * (1 - 1e-12):
+            raise ValueError(f'rotation_angle_total = {ct.theta_tot:.6g} rad is less than a short scan (pi + fan angle = '
+                             f'{need:.6g} rad): projections are missing')
+    if bool(getattr(ct, 'cone', False)) and len(shape) == 4 and shape[1] > 1 and shape[1] != ct.N_rows:
+        raise ValueError(f'covariance sinogram has {shape[1]} rows, the scanner {ct.N_rows}')
+    if ct.N_channels > _native.FBP_VAR_MAX_CHANNELS:
+        raise ValueError(f'{ct.N_channels} channels: the variance filter takes at most {_native.FBP_VAR_MAX_CHANNELS}')
+    return window
+
+
+def recon_covariance_device(cov_d, ct, N_matrix, FOV, ramp, window=None, slices=None):
+    """Noise propagation through the FBP of recon_device: cov_d, device float64 [N_proj, N_channels, T] or [N_proj, N_rows,
+    N_channels, T] - T planes of per-pixel (co)variance of independent sinogram pixels, e.g. the packed triangle of
+    matdecomp.gn_covariance_device - -> the (co)variance of every image pixel, [N_matrix, N_matrix, T] or [rows or slices,
+    N_matrix, N_matrix, T] (float64).  Exact for the discrete operator recon_device applies with the same ``ct``, ``ramp``,
+    ``window`` and ``slices`` (Parker weights of a short scan and Feldkamp's cone branch included): the element-wise square of
+    the FBP matrix applied to every plane (dexct_fbp_var_filter, dexct_fbp_var_backproject, dexct_fdk_var_backproject).  The
+    result is pixel-wise: neighbouring image pixels are correlated, the variance of an ROI mean is not its average."""
+    if not isinstance(cov_d, torch.Tensor) or not cov_d.is_cuda or cov_d.dtype != torch.float64:
+        raise ValueError('cov_d must be a float64 device tensor')
+    window = _check_cov_sino(cov_d.shape, ct, window)
+    lib = _native.load()
+    dev = cov_d.device
+    four_d = cov_d.dim() == 4
+    s = (cov_d if four_d else cov_d[:, None, :, :]).contiguous()
+    n_views, n_rows, n_ch, n_planes = s.shape
+    st = stream_ptr()
+    short = ct.theta_tot < 2 * np.pi - 1e-4
+    cone = bool(getattr(ct, 'cone', False)) and n_rows > 1
+    taps = to_dev(ramp_taps(n_ch, ct.dgamma, ramp, window), torch.float64, dev)
+    weight = to_dev(ct.SID * np.cos(ct.gammas), torch.float64, dev)
+    view_cs = to_dev(ct.view_cs(), torch.float64, dev)
+    qa, qb = torch.empty_like(s), torch.empty_like(s)
+    _native.check(lib.dexct_fbp_var_filter(ptr(s), n_views, n_rows, n_ch, n_planes, ptr(taps), ptr(weight), float(ct.dgamma),
+                                           float(ct.theta_tot) if short else 2 * np.pi, 0, n_views, ptr(qa), ptr(qb), st),
+                  'dexct_fbp_var_filter')
+    if cone:
+        n_slices, z0, dz = slices if slices is not None else default_slices(ct)
+        row_z = ct.row_z()
+        row_w = to_dev(ct.SDD / np.sqrt(ct.SDD ** 2 + (row_z - ct.src_z) ** 2), torch.float64, dev)
+        img = torch.empty((int(n_slices), N_matrix, N_matrix, n_planes), dtype=torch.float64, device=dev)
+        _native.check(lib.dexct_fdk_var_backproject(ptr(qa), ptr(qb), ptr(view_cs), ptr(row_w), n_views, n_ch, n_rows, n_planes,
+                                                    ct.SID, ct.SDD, ct.dgamma, ct.theta_tot / ct.N_proj, float(row_z[0]),
+                                                    float(ct.h), float(ct.src_z), int(N_matrix), float(FOV), int(n_slices),
+                                                    float(z0), float(dz), ptr(img), st), 'dexct_fdk_var_backproject')
+        return img
+    img = torch.empty((n_rows, N_matrix, N_matrix, n_planes), dtype=torch.float64, device=dev)
+    _native.check(lib.dexct_fbp_var_backproject(ptr(qa), ptr(qb), ptr(view_cs), n_views, n_ch, n_rows, n_planes, ct.SID, ct.dgamma,
+                                                ct.theta_tot / ct.N_proj, int(N_matrix), float(FOV), ptr(img), st),
+                  'dexct_fbp_var_backproject')
+    return img if four_d else img[0]
+
+
+def get_recon_covariance(cov_sino, ct, N_matrix, FOV, ramp, window=None, slices=None):
+    """The predicted noise (co)variance of the images get_recon makes from sinograms whose per-pixel (co)variance is
+    ``cov_sino``: [N_proj, N_channels, T] or [N_proj, N_rows, N_channels, T], e.g. what matdecomp.get_basismat_covariance
+    returns (T = 3: var(m1), cov(m1, m2), var(m2)); a single variance sinogram is passed as ``var[..., None]``.  Returns
+    [N_matrix, N_matrix, T] or [rows or slices, N_matrix, N_matrix, T], float64, the layout plots.vmi_noise_map and
+    plots.vmi_variance read.  ``window`` and ``slices`` as for get_recon.  Non-finite entries (a diverged pixel of the
+    decomposition) are set to 0 with a RuntimeWarning - get_recon's rule: they must not smear over the image.  Sinogram
+    pixels are taken as independent; the result is the pixel-wise (co)variance of the FBP image (recon_covariance_device).
+    NumPy in -> NumPy out; a device tensor in -> a device tensor out.  Single process only."""
+    from . import _shard
+    from ._device import to_host
+    tensor_in = isinstance(cov_sino, torch.Tensor)
+    window = _check_cov_sino(cov_sino.shape if tensor_in else np.shape(cov_sino), ct, window)
+    if _shard.world()[1] > 1:
+        raise NotImplementedError('get_recon_covariance runs on a single process')
+    dev = device()
+    cov_d = to_dev(cov_sino if tensor_in else np.asarray(cov_sino, dtype=np.float64), torch.float64, dev)
+    bad = int((~torch.isfinite(cov_d)).sum().item())
+    if bad:
+        import warnings
+        warnings.warn(f'get_recon_covariance: {bad} non-finite covariance value(s) set to 0 before filtering', RuntimeWarning)
+        cov_d = torch.nan_to_num(cov_d, nan=0.0, posinf=0.0, neginf=0.0)
+    out = recon_covariance_device(cov_d, ct, N_matrix, FOV, ramp, window, slices)
+    return out if tensor_in else to_host(out)
+
+
 def make_vmi(E0, M1, M2, HU=True, matcomp1=None, matcomp2=None):
     """Virtual monoenergetic image at E0 [keV] from the two basis-material images - the reference's
     ``make_vmi`` (plots.py:136-144): ``u_p_1 * M1 + u_p_2 * M2`` with the basis mass attenuations at E0, in HU

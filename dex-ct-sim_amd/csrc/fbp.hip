@@ -9,6 +9,7 @@
 // depend on an FFT's rounding); back-projection is pixel driven with the geometry (source offset, fan
 // angle, interpolation weight) in float64 and the filtered values in float32.
 #include "common.h"
+#include "parker.h"
 
 namespace dexct {
 
@@ -171,18 +172,7 @@ __global__ __launch_bounds__(256) void parker_kernel(const float* __restrict__ s
   if (i >= n) return;
   const int c = (int)(i % n_channels);
   const int v = (int)(i / ((size_t)n_rows * n_channels)) + view_offset;
-  const double kPi = 3.14159265358979323846;
-  const double beta = theta_tot * (double)v / (double)n_views_total;
-  const double gam = ((double)c - 0.5 * (double)(n_channels - 1)) * dgamma;
-  const double G = 0.5 * (theta_tot - kPi);
-  double w = 1.0;
-  if (beta < 2.0 * (G - gam)) {
-    const double sn = sin(0.25 * kPi * beta / (G - gam));
-    w = sn * sn;
-  } else if (beta > kPi - 2.0 * gam) {
-    const double sn = sin(0.25 * kPi * (kPi + 2.0 * G - beta) / (G + gam));
-    w = sn * sn;
-  }
+  const double w = parker_weight(theta_tot, v, n_views_total, c, n_channels, dgamma);
   out[i] = (float)(2.0 * w * (double)sino[i]);
 }
 

@@ -14,6 +14,10 @@ for every run in the parameter file, for every dual-energy spectrum pair:
   4. with ``--covariance``: the predicted noise covariance of the two basis-material sinograms per detector pixel
      (matdecomp.get_basismat_covariance at the decomposed line integrals, for the doses of the pair), written next to them as
      ``cov11_sino_float32.bin``, ``cov12_sino_float32.bin``, ``cov22_sino_float32.bin``; air pixels hold 0 like the sinograms.
+  5. with ``--noise-maps`` (needs ``--covariance`` and ``back_project``): that covariance propagated through the FBP
+     (back_project.get_recon_covariance) - the predicted noise (co)variance of the two basis-material images per pixel, written as
+     ``cov11_recon_float32.bin``, ``cov12_recon_float32.bin``, ``cov22_recon_float32.bin`` next to ``mat{1,2}_recon_float32.bin``
+     (computed from the float32 values of the ``cov*_sino`` files, so the two sets of files agree exactly).
 
 Differences from the reference script, all on purpose: inputs are command-line options instead of
 edited source lines (:80-82, :101-103); figures are off unless --show; both spectra of a pair are
@@ -32,7 +36,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 
 import dex_ct_sim_amd as dx  # noqa: E402
-from dex_ct_sim_amd.back_project import get_recon  # noqa: E402
+from dex_ct_sim_amd.back_project import get_recon, get_recon_covariance  # noqa: E402
 from dex_ct_sim_amd.forward_project import get_sinos  # noqa: E402
 from dex_ct_sim_amd.matdecomp import get_basismat_covariance, get_basismat_sinos  # noqa: E402
 
@@ -97,7 +101,15 @@ def main(argv=None):
                     help='also write the predicted noise covariance of each decomposed pair (cov11 / cov12 / cov22 _sino_float32.bin '
                          'beside mat1_sino): of what the Newton solve returns (estimator, the default) or the Cramer-Rao bound '
                          '(crlb); single process only')
+    ap.add_argument('--noise-maps', action='store_true',
+                    help='also write the predicted noise covariance of the basis-material IMAGES (cov11 / cov12 / cov22 '
+                         '_recon_float32.bin beside mat1_recon): the --covariance sinograms propagated through the FBP; needs '
+                         '--covariance, back_project in the parameter file and --recon fbp; single process only')
     args = ap.parse_args(argv)
+    if args.noise_maps and not args.covariance:
+        ap.error('--noise-maps needs --covariance')
+    if args.noise_maps and args.recon != 'fbp':
+        ap.error('--noise-maps propagates the covariance through the FBP: it needs --recon fbp')
     if args.covariance and int(os.environ.get('WORLD_SIZE', '1')) > 1:
         ap.error('--covariance runs on a single process')
     recon_kw = {} if args.recon == 'fbp' else dict(method=args.recon, n_iters=args.recon_iters, n_subsets=args.recon_subsets)
@@ -113,6 +125,8 @@ def main(argv=None):
     args.params = os.path.abspath(args.params)
     args.input_dir = os.path.abspath(args.input_dir)
     all_params = dx.read_parameter_file(args.params, base_dir=os.path.dirname(args.input_dir))
+    if args.noise_maps and not all(params[2] for params in all_params):
+        ap.error('--noise-maps needs runs that back-project: back_project is off in the parameter file')
     for params in all_params:
         run_id, do_fp, do_bp = params[:3]
         ct, phantom, _ = params[3:6]            # the spectrum entry is ignored, as in main.py:92
@@ -175,6 +189,12 @@ def main(argv=None):
                         mat_kw = dict(recon_kw, nonneg=False) if recon_kw else {}
                         recon_raw, _ = get_recon(matsino, ct, specs[0], N_matrix, FOV, ramp, window=args.window, **mat_kw)
                         recon_raw.astype(np.float32).tofile(sub_dir + f'mat{i + 1}_recon_float32.bin')
+                    if args.noise_maps:
+                        print('Propagating the noise covariance through the reconstruction!')
+                        # of the covariance as written (float32): the files of a run agree with each other exactly
+                        cov_img = get_recon_covariance(cov.astype(np.float32), ct, N_matrix, FOV, ramp, window=args.window)
+                        for t, name in enumerate(('cov11', 'cov12', 'cov22')):
+                            cov_img[..., t].astype(np.float32).tofile(sub_dir + f'{name}_recon_float32.bin')
                 print(f'matdecomp finished for {s1}-{s2} : t={time() - t0:.2f}s')
 
 

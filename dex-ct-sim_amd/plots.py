@@ -20,6 +20,8 @@ and the predicted noise of VMI sinograms from the covariance of the decompositio
 
   vmi_variance(cov, E, materials)        ->  variance sinogram of the VMI line integral at E   (HIP: dexct_cov_quadform)
   vmi_noise_sweep(Evals, cov, materials) ->  mean predicted variance per energy, and the energy of least noise
+  vmi_noise_map(cov_img, E, materials)   ->  predicted standard deviation of the VMI at E per image pixel, from the image-domain
+                                             covariance of back_project.get_recon_covariance
 
 A VMI is ``u1(E) M1 + u2(E) M2``; mean, variance and squared error against a piecewise-constant ground truth
 are therefore closed forms in the second-order moments of (M1, M2) per region, which one pass of
@@ -229,6 +231,19 @@ def vmi_variance(cov, E, materials=None):
     _native.check(lib.dexct_cov_quadform(ptr(c), out.numel(), u.shape[0], uvec.ctypes.data, ptr(out), stream_ptr()),
                   'dexct_cov_quadform')
     return out if tensor_in else out.cpu().numpy()
+
+
+def vmi_noise_map(cov_img, E, materials=None, HU=True):
+    """Predicted standard deviation of the VMI at ``E`` [keV] per image pixel: ``sqrt(max(u^T C u, 0))`` of the image-domain
+    covariance ``cov_img`` [..., T] (back_project.get_recon_covariance of a basis-material covariance sinogram) through
+    vmi_variance, in Hounsfield units (times ``1000 / u_water(E)``, the scale of make_vmi) when ``HU``.  Pixel-wise: neighbouring
+    pixels are correlated, so the noise of an ROI mean is not this map's mean over the ROI divided by sqrt(n).  NumPy in -> NumPy
+    out, device tensor in -> device tensor out."""
+    var = vmi_variance(cov_img, E, materials)
+    scale = 1000.0 / float(xcompy.mixatten(WATER, np.array([float(np.atleast_1d(E)[0])]))[0]) if HU else 1.0
+    if isinstance(var, torch.Tensor):
+        return torch.sqrt(torch.clamp(var, min=0.0)) * scale
+    return np.sqrt(np.maximum(var, 0.0)) * scale
 
 
 def vmi_noise_sweep(Evals, cov, materials=None, mask=None):

@@ -632,6 +632,49 @@ int dexct_fdk_backproject(const float* q, const double* view_cs, const float* ro
                           double row_z0, double row_dz, double src_z, int32_t n_matrix, double fov, int32_t n_slices,
                           double z0, double dz, float* image, void* stream);
 
+/* Noise propagation through the filtered back-projection above (csrc/fbp_var.hip): the (co)variance of every image pixel
+ * from the (co)variance of the sinogram pixels, which are taken as independent (the library's noise model).  The FBP is linear,
+ * image = M sino, so the result is (M o M) s, the element-wise square of the FBP matrix applied to s - exactly, for the discrete
+ * operator of dexct_fbp_parker + dexct_fbp_filter + dexct_fbp_backproject / dexct_fdk_backproject.  It is linear in s: s may be a
+ * variance or the cross-covariance of two sinograms that go through the same FBP, and the n_planes planes of a packed covariance
+ * (the upper triangle of dexct_gn_covariance: 00, 01, 11, ...) go through it side by side.  Everything is float64.
+ *   dexct_fbp_var_filter:  A[line][n] = dgamma^2 sum_m s[line][m] weight[m]^2 P^2 taps[(n - m) + n_channels - 1]^2
+ *                          B[line][n] = dgamma^2 sum_m s[line][m] weight[m]^2 P^2 taps[(n - m) + n_channels - 1]
+ *                                                                               * taps[(n + 1 - m) + n_channels - 1]
+ *                          A: the variance of the filtered sample n, B: the covariance of the samples n and n + 1; B of the
+ *                          last channel is written as 0.  line = (view, row); weight[m] = SID cos(gamma_m) as for
+ *                          dexct_fbp_filter (squared here), taps the 2 n_channels - 1 float64 ramp taps.  P = 2 w_Parker(view_offset
+ *                          + view, m) of a short scan over theta_tot < 2 pi with n_views_total views (the arguments and the
+ *                          condition of dexct_fbp_parker: DEXCT_EINVAL if theta_tot does not cover pi + the fan angle), P = 1
+ *                          for theta_tot >= 2 pi.
+ *     cov      [n_views][n_rows][n_channels][n_planes]: the packed covariance with the sinogram's axes in front
+ *     qa, qb   [n_views][n_rows][n_channels][n_planes]: A and B in the layout of cov
+ *     n_channels <= DEXCT_FBP_VAR_MAX_CHANNELS (line and taps sit in 24 n_channels - 8 bytes of LDS): DEXCT_ERANGE beyond, also
+ *     for more than 65535 planes or 2^31 - 1 lines.
+ *   dexct_fbp_var_backproject: image_cov[row][iy][ix][plane] = dbeta^2 sum_views [ (1 - w)^2 A[k] + w^2 A[k + 1]
+ *                          + 2 w (1 - w) B[k] ] / L^4 with the channel k, the interpolation weight w, the source distance L and
+ *                          the in-fan condition of dexct_fbp_backproject (same arguments); a pixel no view sees holds 0.
+ *   dexct_fdk_var_backproject: the arguments of dexct_fdk_backproject with qa, qb, n_planes and a float64 row_weight.  Rows are
+ *                          independent: with V_r = (1 - w)^2 A[r][k] + w^2 A[r][k + 1] + 2 w (1 - w) B[r][k] a view adds
+ *                          [ (1 - w_r)^2 row_weight[r0]^2 V_r0 + w_r^2 row_weight[r0 + 1]^2 V_(r0 + 1) ] / L^4;
+ *                          image_cov [slice][iy][ix][plane].
+ * image_cov has the pixel-major layout dexct_cov_quadform reads.  It is the pixel-wise (co)variance: neighbouring image pixels are
+ * correlated, so the variance of an ROI mean is not its average.  DEXCT_EINVAL for null pointers, n_planes < 1 and the argument
+ * errors of the float32 entry points; DEXCT_ERANGE for their grid limits.  Every argument error is returned before the first launch.
+ * The back-projections launch once per group of 6, 3 or 1 planes: a launch the runtime refuses (DEXCT_EHIP) ends the call there, and
+ * the planes of the groups before it have been written. */
+#define DEXCT_FBP_VAR_MAX_CHANNELS 2730
+int dexct_fbp_var_filter(const double* cov, int32_t n_views, int32_t n_rows, int32_t n_channels, int32_t n_planes,
+                         const double* taps, const double* weight, double dgamma, double theta_tot, int32_t view_offset,
+                         int32_t n_views_total, double* qa, double* qb, void* stream);
+int dexct_fbp_var_backproject(const double* qa, const double* qb, const double* view_cs, int32_t n_views,
+                              int32_t n_channels, int32_t n_rows, int32_t n_planes, double sid, double dgamma,
+                              double dbeta, int32_t n_matrix, double fov, double* image_cov, void* stream);
+int dexct_fdk_var_backproject(const double* qa, const double* qb, const double* view_cs, const double* row_weight,
+                              int32_t n_views, int32_t n_channels, int32_t n_rows, int32_t n_planes, double sid, double sdd,
+                              double dgamma, double dbeta, double row_z0, double row_dz, double src_z, int32_t n_matrix,
+                              double fov, int32_t n_slices, double z0, double dz, double* image_cov, void* stream);
+
 /* Virtual monoenergetic image (plots.py:136-144): out = u1*m1 + u2*m2 (basis-material images m1, m2, n pixels;
  * u1, u2 mass attenuation of the basis materials at the chosen energy), in HU against u_water when hu != 0. */
 int dexct_vmi(const float* m1, const float* m2, int64_t n, double u1, double u2, double u_water, int32_t hu,
