@@ -84,6 +84,35 @@ def default_slices(ct):
     return ct.N_rows, -0.5 * (ct.N_rows - 1) * ct.h_iso, ct.h_iso
 
 
+def _short_scan(ct):
+    """Is the rotation (``rotation_angle_total``, input/params.txt:24) a short scan: one for Parker's weights, which make every
+    ray count once?  Refuses what the FBP does not reconstruct."""
+    if ct.theta_tot > 2 * np.pi + 1e-4:
+        raise ValueError(f'rotation_angle_total = {ct.theta_tot:.6g} exceeds 2 pi: more than one rotation is not reconstructed')
+    if ct.theta_tot >= 2 * np.pi - 1e-4:
+        return False
+    need = np.pi + (ct.N_channels - 1) * ct.dgamma
+    if ct.theta_tot < need * (1 - 1e-12):
+        raise ValueError(f'rotation_angle_total = {ct.theta_tot:.6g} rad is less than a short scan (pi + fan angle = '
+                         f'{need:.6g} rad): projections are missing')
+    return True
+
+
+def _fbp_inputs(ct, ramp, window, cone, slices, dtype, dev):
+    """What the filter and the back-projection read besides the sinogram, on the device: the taps and the channel weight
+    SID cos(gamma) in ``dtype`` (float32 for the image, float64 for its covariance), (cos, sin) of the views in float64 and,
+    for a cone, ``(row weights in dtype, z of row 0, n_slices, z0, dz)`` - else None."""
+    taps = to_dev(ramp_taps(ct.N_channels, ct.dgamma, ramp, window), dtype, dev)
+    weight = to_dev(ct.SID * np.cos(ct.gammas), dtype, dev)
+    view_cs = to_dev(ct.view_cs(), torch.float64, dev)
+    if not cone:
+        return taps, weight, view_cs, None
+    n_slices, z0, dz = slices if slices is not None else default_slices(ct)
+    row_z = ct.row_z()
+    row_w = to_dev(ct.SDD / np.sqrt(ct.SDD ** 2 + (row_z - ct.src_z) ** 2), dtype, dev)
+    return taps, weight, view_cs, (row_w, float(row_z[0]), int(n_slices), float(z0), float(dz))
+
+
 def recon_device(sino_d, ct, N_matrix, FOV, ramp, window=None, slices=None, bhc=None, method='fbp', n_iters=20, n_subsets=1,
                  relax=1.0, init='fbp', nonneg=True, history=None):
     """sino_d: device float32 [N_proj, N_channels] or [N_proj, N_rows, N_channels] -> image tensor
@@ -106,36 +135,25 @@ def recon_device(sino_d, ct, N_matrix, FOV, ramp, window=None, slices=None, bhc=
     if n_views != ct.N_proj or n_ch != ct.N_channels:
         raise ValueError(f'sinogram {tuple(sino_d.shape)} does not match the scanner ({ct.N_proj} x {ct.N_channels})')
     st = stream_ptr()
-    if ct.theta_tot > 2 * np.pi + 1e-4:
-        raise ValueError(f'rotation_angle_total = {ct.theta_tot:.6g} exceeds 2 pi: more than one rotation is not reconstructed')
-    if ct.theta_tot < 2 * np.pi - 1e-4:
-        # a short scan (rotation_angle_total, input/params.txt:24): Parker's weights make every ray count once
-        need = np.pi + (n_ch - 1) * ct.dgamma
-        if ct.theta_tot < need * (1 - 1e-12):
-            raise ValueError(f'rotation_angle_total = {ct.theta_tot:.6g} rad is less than a short scan (pi + fan angle = '
-                             f'{need:.6g} rad): projections are missing')
+    if _short_scan(ct):
         sw = torch.empty_like(s)
         _native.check(lib.dexct_fbp_parker(ptr(s), n_views, n_rows, n_ch, float(ct.theta_tot), float(ct.dgamma), 0, n_views,
                                            ptr(sw), st), 'dexct_fbp_parker')
         s = sw
     cone = bool(getattr(ct, 'cone', False)) and n_rows > 1
-    taps = to_dev(ramp_taps(n_ch, ct.dgamma, ramp, window or default_window()), torch.float32, dev)
-    weight = to_dev(ct.SID * np.cos(ct.gammas), torch.float32, dev)
-    view_cs = to_dev(ct.view_cs(), torch.float64, dev)
+    if cone and n_rows != ct.N_rows:
+        raise ValueError(f'sinogram has {n_rows} rows, the scanner {ct.N_rows}')
+    taps, weight, view_cs, fdk = _fbp_inputs(ct, ramp, window or default_window(), cone, slices, torch.float32, dev)
     q = torch.empty_like(s)
     _native.check(lib.dexct_fbp_filter(ptr(s), ptr(taps), ptr(weight), n_views * n_rows, n_ch, ct.dgamma, ptr(q), st),
                   'dexct_fbp_filter')
     if cone:
-        if n_rows != ct.N_rows:
-            raise ValueError(f'sinogram has {n_rows} rows, the scanner {ct.N_rows}')
-        n_slices, z0, dz = slices if slices is not None else default_slices(ct)
-        row_z = ct.row_z()
-        row_w = to_dev(ct.SDD / np.sqrt(ct.SDD ** 2 + (row_z - ct.src_z) ** 2), torch.float32, dev)
-        img = torch.empty((int(n_slices), N_matrix, N_matrix), dtype=torch.float32, device=dev)
+        row_w, row_z0, n_slices, z0, dz = fdk
+        img = torch.empty((n_slices, N_matrix, N_matrix), dtype=torch.float32, device=dev)
         _native.check(lib.dexct_fdk_backproject(ptr(q), ptr(view_cs), ptr(row_w), n_views, n_ch, n_rows, ct.SID, ct.SDD,
-                                                ct.dgamma, ct.theta_tot / ct.N_proj, float(row_z[0]), float(ct.h),
-                                                float(ct.src_z), int(N_matrix), float(FOV), int(n_slices), float(z0),
-                                                float(dz), ptr(img), st), 'dexct_fdk_backproject')
+                                                ct.dgamma, ct.theta_tot / ct.N_proj, row_z0, float(ct.h), float(ct.src_z),
+                                                int(N_matrix), float(FOV), n_slices, z0, dz, ptr(img), st),
+                      'dexct_fdk_backproject')
         return img
     img = torch.empty((n_rows, N_matrix, N_matrix), dtype=torch.float32, device=dev)
     _native.check(lib.dexct_fbp_backproject(ptr(q), ptr(view_cs), n_views, n_ch, n_rows, ct.SID, ct.dgamma,
@@ -218,13 +236,7 @@ def _check_cov_sino(shape, ct, window):
     window = window or default_window()
     if window not in WINDOWS:
         raise ValueError(f'unknown filter window {window!r}; choose from {sorted(WINDOWS)}')
-    if ct.theta_tot > 2 * np.pi + 1e-4:
-        raise ValueError(f'rotation_angle_total = {ct.theta_tot:.6g} exceeds 2 pi: more than one rotation is not reconstructed')
-    if ct.theta_tot < 2 * np.pi - 1e-4:
-        need = np.pi + (ct.N_channels - 1) * ct.dgamma
-        if ct.theta_tot < need * (1 - 1e-12):
-            raise ValueError(f'rotation_angle_total = {ct.theta_tot:.6g} rad is less than a short scan (pi + fan angle = '
-                             f'{need:.6g} rad): projections are missing')
+    _short_scan(ct)
     if bool(getattr(ct, 'cone', False)) and len(shape) == 4 and shape[1] > 1 and shape[1] != ct.N_rows:
         raise ValueError(f'covariance sinogram has {shape[1]} rows, the scanner {ct.N_rows}')
     if ct.N_channels > _native.FBP_VAR_MAX_CHANNELS:
@@ -249,24 +261,20 @@ def recon_covariance_device(cov_d, ct, N_matrix, FOV, ramp, window=None, slices=
     s = (cov_d if four_d else cov_d[:, None, :, :]).contiguous()
     n_views, n_rows, n_ch, n_planes = s.shape
     st = stream_ptr()
-    short = ct.theta_tot < 2 * np.pi - 1e-4
+    short = _short_scan(ct)
     cone = bool(getattr(ct, 'cone', False)) and n_rows > 1
-    taps = to_dev(ramp_taps(n_ch, ct.dgamma, ramp, window), torch.float64, dev)
-    weight = to_dev(ct.SID * np.cos(ct.gammas), torch.float64, dev)
-    view_cs = to_dev(ct.view_cs(), torch.float64, dev)
+    taps, weight, view_cs, fdk = _fbp_inputs(ct, ramp, window, cone, slices, torch.float64, dev)
     qa, qb = torch.empty_like(s), torch.empty_like(s)
     _native.check(lib.dexct_fbp_var_filter(ptr(s), n_views, n_rows, n_ch, n_planes, ptr(taps), ptr(weight), float(ct.dgamma),
                                            float(ct.theta_tot) if short else 2 * np.pi, 0, n_views, ptr(qa), ptr(qb), st),
                   'dexct_fbp_var_filter')
     if cone:
-        n_slices, z0, dz = slices if slices is not None else default_slices(ct)
-        row_z = ct.row_z()
-        row_w = to_dev(ct.SDD / np.sqrt(ct.SDD ** 2 + (row_z - ct.src_z) ** 2), torch.float64, dev)
-        img = torch.empty((int(n_slices), N_matrix, N_matrix, n_planes), dtype=torch.float64, device=dev)
+        row_w, row_z0, n_slices, z0, dz = fdk
+        img = torch.empty((n_slices, N_matrix, N_matrix, n_planes), dtype=torch.float64, device=dev)
         _native.check(lib.dexct_fdk_var_backproject(ptr(qa), ptr(qb), ptr(view_cs), ptr(row_w), n_views, n_ch, n_rows, n_planes,
-                                                    ct.SID, ct.SDD, ct.dgamma, ct.theta_tot / ct.N_proj, float(row_z[0]),
-                                                    float(ct.h), float(ct.src_z), int(N_matrix), float(FOV), int(n_slices),
-                                                    float(z0), float(dz), ptr(img), st), 'dexct_fdk_var_backproject')
+                                                    ct.SID, ct.SDD, ct.dgamma, ct.theta_tot / ct.N_proj, row_z0, float(ct.h),
+                                                    float(ct.src_z), int(N_matrix), float(FOV), n_slices, z0, dz, ptr(img), st),
+                      'dexct_fdk_var_backproject')
         return img
     img = torch.empty((n_rows, N_matrix, N_matrix, n_planes), dtype=torch.float64, device=dev)
     _native.check(lib.dexct_fbp_var_backproject(ptr(qa), ptr(qb), ptr(view_cs), n_views, n_ch, n_rows, n_planes, ct.SID, ct.dgamma,

@@ -9,6 +9,7 @@
 // depend on an FFT's rounding); back-projection is pixel driven with the geometry (source offset, fan
 // angle, interpolation weight) in float64 and the filtered values in float32.
 #include "common.h"
+#include "fan_pixel.h"
 #include "parker.h"
 
 namespace dexct {
@@ -56,23 +57,18 @@ __global__ __launch_bounds__(kFbpBlock) void fbp_backproject_kernel(const float*
   const int iy = blockIdx.y * 4 + (threadIdx.x >> 6);
   const int row0 = blockIdx.z * R;
   if (ix >= g.n_matrix || iy >= g.n_matrix) return;
-  const double x = (ix - 0.5 * g.n_matrix + 0.5) * g.pixel, y = (iy - 0.5 * g.n_matrix + 0.5) * g.pixel;
+  const double x = pixel_centre(ix, g.n_matrix, g.pixel), y = pixel_centre(iy, g.n_matrix, g.pixel);
   const double inv_dg = 1.0 / g.dgamma, half = 0.5 * (g.n_channels - 1);
   const int n_rows_here = g.n_rows - row0 < R ? g.n_rows - row0 : R;
   float acc[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) acc[r] = 0.0f;
   for (int v = 0; v < g.n_views; ++v) {
-    const double cb = view_cs[2 * v], sb = view_cs[2 * v + 1];   // wave-uniform
-    const double dx = x - g.sid * cb, dy = y - g.sid * sb;
-    const double dot = -(cb * dx + sb * dy), cross = -(cb * dy - sb * dx);
-    const double pos = atan2(cross, dot) * inv_dg + half;
-    const double fl = floor(pos);
-    const int k = (int)fl;
-    if (k >= 0 && k < g.n_channels - 1) {
-      const float w = (float)(pos - fl);
-      const float l2 = (float)(dx * dx + dy * dy);
-      const float* ql = q + ((size_t)v * g.n_rows + row0) * g.n_channels + k;
+    const FanHit h = fan_hit(x, y, g.sid, view_cs[2 * v], view_cs[2 * v + 1], inv_dg, half);   // view_cs: wave-uniform
+    if (h.in_fan(g.n_channels)) {
+      const float w = (float)h.frac;
+      const float l2 = (float)(h.dx * h.dx + h.dy * h.dy);
+      const float* ql = q + ((size_t)v * g.n_rows + row0) * g.n_channels + h.k;
 #pragma unroll
       for (int r = 0; r < R; ++r) {
         if (r < n_rows_here) {
@@ -109,34 +105,27 @@ __global__ __launch_bounds__(kFbpBlock) void fdk_backproject_kernel(const float*
   const int iy = blockIdx.y * 4 + (threadIdx.x >> 6);
   const int k0 = blockIdx.z * R;
   if (ix >= g.n_matrix || iy >= g.n_matrix) return;
-  const double x = (ix - 0.5 * g.n_matrix + 0.5) * g.pixel, y = (iy - 0.5 * g.n_matrix + 0.5) * g.pixel;
+  const double x = pixel_centre(ix, g.n_matrix, g.pixel), y = pixel_centre(iy, g.n_matrix, g.pixel);
   const double inv_dg = 1.0 / g.dgamma, half = 0.5 * (g.n_channels - 1), inv_rdz = 1.0 / g.row_dz;
   const int n_here = g.n_slices - k0 < R ? g.n_slices - k0 : R;
   float acc[R];
 #pragma unroll
   for (int r = 0; r < R; ++r) acc[r] = 0.0f;
   for (int v = 0; v < g.n_views; ++v) {
-    const double cb = view_cs[2 * v], sb = view_cs[2 * v + 1];
-    const double dx = x - g.sid * cb, dy = y - g.sid * sb;
-    const double dot = -(cb * dx + sb * dy), cross = -(cb * dy - sb * dx);
-    const double pos = atan2(cross, dot) * inv_dg + half;
-    const double fl = floor(pos);
-    const int k = (int)fl;
-    if (k < 0 || k >= g.n_channels - 1) continue;
-    const float w = (float)(pos - fl);
-    const double l2 = dx * dx + dy * dy;
+    const FanHit h = fan_hit(x, y, g.sid, view_cs[2 * v], view_cs[2 * v + 1], inv_dg, half);
+    if (!h.in_fan(g.n_channels)) continue;
+    const float w = (float)h.frac;
+    const double l2 = h.dx * h.dx + h.dy * h.dy;
     const float inv_l2 = (float)(1.0 / l2);
     const double mag = g.sdd / sqrt(l2);                  // magnification of heights from the voxel to the detector
-    const float* qv = q + (size_t)v * g.n_rows * g.n_channels + k;
+    const float* qv = q + (size_t)v * g.n_rows * g.n_channels + h.k;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       if (r < n_here) {
-        const double z = g.z0 + (k0 + r) * g.dz;
-        const double rpos = (g.src_z + (z - g.src_z) * mag - g.row_z0) * inv_rdz;
-        const double rfl = floor(rpos);
-        const int r0 = (int)rfl;
-        if (r0 >= 0 && r0 < g.n_rows - 1) {
-          const float wr = (float)(rpos - rfl);
+        const RowHit rh = fdk_row(g.z0 + (k0 + r) * g.dz, g.src_z, mag, g.row_z0, inv_rdz);
+        if (rh.on_detector(g.n_rows)) {
+          const int r0 = rh.r0;
+          const float wr = (float)rh.frac;
           const float* qa = qv + (size_t)r0 * g.n_channels;
           const float* qb = qa + g.n_channels;
           const float va = ((1.0f - w) * qa[0] + w * qa[1]) * row_weight[r0];
@@ -194,10 +183,8 @@ int dexct_fbp_parker(const float* sino, int32_t n_views, int32_t n_rows, int32_t
   if (!sino || !out || n_views < 1 || n_rows < 1 || n_channels < 1 || n_views_total < n_views || view_offset < 0 ||
       view_offset + n_views > n_views_total)
     return DEXCT_EINVAL;
-  const double kPi = 3.14159265358979323846;
-  const double half_fan = 0.5 * (double)(n_channels - 1) * dgamma;
   // a short scan needs pi + the full fan angle; 2 pi and beyond is not a short scan
-  if (!(dgamma > 0.0) || !(theta_tot < 2.0 * kPi) || !(0.5 * (theta_tot - kPi) >= half_fan * (1.0 - 1e-12))) return DEXCT_EINVAL;
+  if (!(dgamma > 0.0) || !(theta_tot < 2.0 * kPi) || !short_scan_complete(theta_tot, n_channels, dgamma)) return DEXCT_EINVAL;
   const size_t n = (size_t)n_views * n_rows * n_channels;
   const size_t nblk = (n + 255) / 256;
   if (nblk > 0x7FFFFFFFull) return DEXCT_ERANGE;
@@ -210,9 +197,8 @@ int dexct_fbp_parker(const float* sino, int32_t n_views, int32_t n_rows, int32_t
 int dexct_fbp_backproject(const float* q, const double* view_cs, int32_t n_views, int32_t n_channels, int32_t n_rows,
                           double sid, double dgamma, double dbeta, int32_t n_matrix, double fov, float* image,
                           void* stream) {
-  if (!q || !view_cs || !image || n_views <= 0 || n_channels < 2 || n_rows <= 0 || n_matrix <= 0) return DEXCT_EINVAL;
-  if (n_rows > 65535 || (n_matrix + 3) / 4 > 65535) return DEXCT_ERANGE;
-  if (!(sid > 0) || !(dgamma > 0) || !(fov > 0)) return DEXCT_EINVAL;
+  const int bad = check_fan_args(q && view_cs && image, n_views, n_channels, n_rows, n_matrix, sid, dgamma, fov);
+  if (bad) return bad;
   FbpGeom g{n_views, n_channels, n_rows, n_matrix, sid, dgamma, dbeta, fov / n_matrix};
   if (n_rows >= 8) {
     dim3 grid((n_matrix + 63) / 64, (n_matrix + 3) / 4, (n_rows + 7) / 8);
@@ -229,11 +215,9 @@ int dexct_fdk_backproject(const float* q, const double* view_cs, const float* ro
                           int32_t n_channels, int32_t n_rows, double sid, double sdd, double dgamma, double dbeta,
                           double row_z0, double row_dz, double src_z, int32_t n_matrix, double fov, int32_t n_slices,
                           double z0, double dz, float* image, void* stream) {
-  if (!q || !view_cs || !row_weight || !image || n_views <= 0 || n_channels < 2 || n_rows < 2 || n_matrix <= 0 ||
-      n_slices <= 0)
-    return DEXCT_EINVAL;
-  if (!(sid > 0) || !(sdd >= sid) || !(dgamma > 0) || !(fov > 0) || !(row_dz > 0) || !(dz > 0)) return DEXCT_EINVAL;
-  if ((n_slices + 3) / 4 > 65535 || (n_matrix + 3) / 4 > 65535) return DEXCT_ERANGE;
+  const int bad = check_cone_args(q && view_cs && row_weight && image, n_views, n_channels, n_rows, n_matrix, n_slices, 4, sid, sdd,
+                                  dgamma, fov, row_dz, dz);
+  if (bad) return bad;
   FdkGeom g{n_views, n_channels, n_rows, n_matrix, n_slices, sid, sdd, dgamma, dbeta, fov / n_matrix,
             row_z0, row_dz, src_z, z0, dz};
   dim3 grid((n_matrix + 63) / 64, (n_matrix + 3) / 4, (n_slices + 3) / 4);

@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "fan_pixel.h"
 #include "parker.h"
 
 namespace dexct {
@@ -80,7 +81,7 @@ struct VarGeom {
 };
 
 // One thread per pixel (x, y), T planes from plane0 on and R consecutive rows.  qa, qb are [view][row][channel][plane].
-// The geometry of a (pixel, view) pair is that of fbp_backproject_kernel, in the same operations; the three
+// The geometry of a (pixel, view) pair is that of fbp_backproject_kernel: both call fan_hit (fan_pixel.h); the three
 // interpolation weights carry 1 / L^4 and are formed once per pair, then applied to T x R accumulators in registers.
 template <int T, int R>
 __global__ __launch_bounds__(kVarBlock) void fbp_var_backproject_kernel(const double* __restrict__ qa,
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(kVarBlock) void fbp_var_backproject_kernel(const do
   const int iy = blockIdx.y * 4 + (threadIdx.x >> 6);
   const int row0 = blockIdx.z * R;
   if (ix >= g.n_matrix || iy >= g.n_matrix) return;
-  const double x = (ix - 0.5 * g.n_matrix + 0.5) * g.pixel, y = (iy - 0.5 * g.n_matrix + 0.5) * g.pixel;
+  const double x = pixel_centre(ix, g.n_matrix, g.pixel), y = pixel_centre(iy, g.n_matrix, g.pixel);
   const double inv_dg = 1.0 / g.dgamma, half = 0.5 * (g.n_channels - 1);
   const int n_rows_here = g.n_rows - row0 < R ? g.n_rows - row0 : R;
   const size_t row_stride = (size_t)g.n_channels * g.n_planes;
@@ -101,18 +102,13 @@ __global__ __launch_bounds__(kVarBlock) void fbp_var_backproject_kernel(const do
 #pragma unroll
     for (int t = 0; t < T; ++t) acc[r][t] = 0.0;
   for (int v = 0; v < g.n_views; ++v) {
-    const double cb = view_cs[2 * v], sb = view_cs[2 * v + 1];   // wave-uniform
-    const double dx = x - g.sid * cb, dy = y - g.sid * sb;
-    const double dot = -(cb * dx + sb * dy), cross = -(cb * dy - sb * dx);
-    const double pos = atan2(cross, dot) * inv_dg + half;
-    const double fl = floor(pos);
-    const int k = (int)fl;
-    if (k >= 0 && k < g.n_channels - 1) {
-      const double w = pos - fl, u = 1.0 - w;
-      const double l2 = dx * dx + dy * dy;
+    const FanHit h = fan_hit(x, y, g.sid, view_cs[2 * v], view_cs[2 * v + 1], inv_dg, half);   // view_cs: wave-uniform
+    if (h.in_fan(g.n_channels)) {
+      const double w = h.frac, u = 1.0 - w;
+      const double l2 = h.dx * h.dx + h.dy * h.dy;
       const double inv_l4 = 1.0 / (l2 * l2);
       const double c0 = u * u * inv_l4, c1 = w * w * inv_l4, c2 = 2.0 * w * u * inv_l4;
-      const size_t o = (((size_t)v * g.n_rows + row0) * g.n_channels + k) * g.n_planes + g.plane0;
+      const size_t o = (((size_t)v * g.n_rows + row0) * g.n_channels + h.k) * g.n_planes + g.plane0;
       const double* pa = qa + o;
       const double* pb = qb + o;
 #pragma unroll
@@ -156,7 +152,7 @@ __global__ __launch_bounds__(kVarBlock) void fdk_var_backproject_kernel(const do
   const int iy = blockIdx.y * 4 + (threadIdx.x >> 6);
   const int k0 = blockIdx.z * R;
   if (ix >= g.n_matrix || iy >= g.n_matrix) return;
-  const double x = (ix - 0.5 * g.n_matrix + 0.5) * g.pixel, y = (iy - 0.5 * g.n_matrix + 0.5) * g.pixel;
+  const double x = pixel_centre(ix, g.n_matrix, g.pixel), y = pixel_centre(iy, g.n_matrix, g.pixel);
   const double inv_dg = 1.0 / g.dgamma, half = 0.5 * (g.n_channels - 1), inv_rdz = 1.0 / g.row_dz;
   const int n_here = g.n_slices - k0 < R ? g.n_slices - k0 : R;
   const size_t row_stride = (size_t)g.n_channels * g.n_planes;
@@ -166,28 +162,21 @@ __global__ __launch_bounds__(kVarBlock) void fdk_var_backproject_kernel(const do
 #pragma unroll
     for (int t = 0; t < T; ++t) acc[r][t] = 0.0;
   for (int v = 0; v < g.n_views; ++v) {
-    const double cb = view_cs[2 * v], sb = view_cs[2 * v + 1];
-    const double dx = x - g.sid * cb, dy = y - g.sid * sb;
-    const double dot = -(cb * dx + sb * dy), cross = -(cb * dy - sb * dx);
-    const double pos = atan2(cross, dot) * inv_dg + half;
-    const double fl = floor(pos);
-    const int k = (int)fl;
-    if (k < 0 || k >= g.n_channels - 1) continue;
-    const double w = pos - fl, u = 1.0 - w;
+    const FanHit h = fan_hit(x, y, g.sid, view_cs[2 * v], view_cs[2 * v + 1], inv_dg, half);
+    if (!h.in_fan(g.n_channels)) continue;
+    const double w = h.frac, u = 1.0 - w;
     const double c0 = u * u, c1 = w * w, c2 = 2.0 * w * u;
-    const double l2 = dx * dx + dy * dy;
+    const double l2 = h.dx * h.dx + h.dy * h.dy;
     const double inv_l4 = 1.0 / (l2 * l2);
     const double mag = g.sdd / sqrt(l2);                  // magnification of heights from the voxel to the detector
-    const size_t ov = ((size_t)v * g.n_rows * g.n_channels + k) * g.n_planes + g.plane0;
+    const size_t ov = ((size_t)v * g.n_rows * g.n_channels + h.k) * g.n_planes + g.plane0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       if (r < n_here) {
-        const double z = g.z0 + (k0 + r) * g.dz;
-        const double rpos = (g.src_z + (z - g.src_z) * mag - g.row_z0) * inv_rdz;
-        const double rfl = floor(rpos);
-        const int r0 = (int)rfl;
-        if (r0 >= 0 && r0 < g.n_rows - 1) {
-          const double wr = rpos - rfl, ur = 1.0 - wr;
+        const RowHit rh = fdk_row(g.z0 + (k0 + r) * g.dz, g.src_z, mag, g.row_z0, inv_rdz);
+        if (rh.on_detector(g.n_rows)) {
+          const int r0 = rh.r0;
+          const double wr = rh.frac, ur = 1.0 - wr;
           const double ra = row_weight[r0], rb = row_weight[r0 + 1];
           const double fa = ur * ur * (ra * ra) * inv_l4, fb = wr * wr * (rb * rb) * inv_l4;
           const double* pa = qa + ov + (size_t)r0 * row_stride;
@@ -270,11 +259,9 @@ int dexct_fbp_var_filter(const double* cov, int32_t n_views, int32_t n_rows, int
   if (!cov || !taps || !weight || !qa || !qb || n_views < 1 || n_rows < 1 || n_channels < 2 || n_planes < 1 ||
       n_views_total < n_views || view_offset < 0 || view_offset > n_views_total - n_views)
     return DEXCT_EINVAL;
-  const double kPi = 3.14159265358979323846;
   if (!(dgamma > 0.0) || !(theta_tot > 0.0)) return DEXCT_EINVAL;
   // a short scan needs pi + the full fan angle (dexct_fbp_parker's rule); 2 pi and beyond carries no Parker weight
-  if (theta_tot < 2.0 * kPi && !(0.5 * (theta_tot - kPi) >= 0.5 * (double)(n_channels - 1) * dgamma * (1.0 - 1e-12)))
-    return DEXCT_EINVAL;
+  if (theta_tot < 2.0 * kPi && !short_scan_complete(theta_tot, n_channels, dgamma)) return DEXCT_EINVAL;
   if (n_channels > DEXCT_FBP_VAR_MAX_CHANNELS || n_planes > 65535 || (int64_t)n_views * n_rows > 0x7FFFFFFFll)
     return DEXCT_ERANGE;
   const size_t lds = (size_t)(3 * n_channels - 1) * sizeof(double);
@@ -288,10 +275,9 @@ int dexct_fbp_var_filter(const double* cov, int32_t n_views, int32_t n_rows, int
 int dexct_fbp_var_backproject(const double* qa, const double* qb, const double* view_cs, int32_t n_views,
                               int32_t n_channels, int32_t n_rows, int32_t n_planes, double sid, double dgamma,
                               double dbeta, int32_t n_matrix, double fov, double* image_cov, void* stream) {
-  if (!qa || !qb || !view_cs || !image_cov || n_views <= 0 || n_channels < 2 || n_rows <= 0 || n_planes < 1 || n_matrix <= 0)
-    return DEXCT_EINVAL;
-  if (n_rows > 65535 || (n_matrix + 3) / 4 > 65535) return DEXCT_ERANGE;
-  if (!(sid > 0) || !(dgamma > 0) || !(fov > 0)) return DEXCT_EINVAL;
+  const int bad = check_fan_args(qa && qb && view_cs && image_cov && n_planes >= 1, n_views, n_channels, n_rows, n_matrix, sid,
+                                 dgamma, fov);
+  if (bad) return bad;
   VarGeom g{n_views, n_channels, n_rows, n_matrix, n_planes, 0, sid, dgamma, dbeta, fov / n_matrix};
   hipStream_t st = as_stream(stream);
   return for_plane_groups(n_planes, [&](auto planes, int plane0) {
@@ -304,11 +290,9 @@ int dexct_fdk_var_backproject(const double* qa, const double* qb, const double* 
                               int32_t n_views, int32_t n_channels, int32_t n_rows, int32_t n_planes, double sid, double sdd,
                               double dgamma, double dbeta, double row_z0, double row_dz, double src_z, int32_t n_matrix,
                               double fov, int32_t n_slices, double z0, double dz, double* image_cov, void* stream) {
-  if (!qa || !qb || !view_cs || !row_weight || !image_cov || n_views <= 0 || n_channels < 2 || n_rows < 2 || n_planes < 1 ||
-      n_matrix <= 0 || n_slices <= 0)
-    return DEXCT_EINVAL;
-  if (!(sid > 0) || !(sdd >= sid) || !(dgamma > 0) || !(fov > 0) || !(row_dz > 0) || !(dz > 0)) return DEXCT_EINVAL;
-  if ((n_slices + 1) / 2 > 65535 || (n_matrix + 3) / 4 > 65535) return DEXCT_ERANGE;
+  const int bad = check_cone_args(qa && qb && view_cs && row_weight && image_cov && n_planes >= 1, n_views, n_channels, n_rows,
+                                  n_matrix, n_slices, 2, sid, sdd, dgamma, fov, row_dz, dz);
+  if (bad) return bad;
   FdkVarGeom g{n_views, n_channels, n_rows, n_matrix, n_slices, n_planes, 0, sid, sdd, dgamma, dbeta, fov / n_matrix,
                row_z0, row_dz, src_z, z0, dz};
   hipStream_t st = as_stream(stream);

@@ -21,36 +21,20 @@
 // number of 1e3 .. 1e5, which a float32 exponential would turn into 1e-3 .. 1e-2 of the result.
 //
 // dexct_cov_quadform is the element-wise u^T C_p u: the variance of the VMI line integral sum_m u_m a_m.
-#include "common.h"
-#include "exp_table.h"
+#include "gn_pixel.h"
 
 namespace dexct {
 namespace {
 
+using namespace gnpix;
 using exptab::exp_tab;
 using exptab::kExpClip;
 using exptab::kExpScale;
 using exptab::kPowN;
 using exptab::rcp_f64;
 
-constexpr int kBlock = 256;
-constexpr int kHeader = 16;                    // doubles: [0] = energies kept (as a double), the rest 0
-constexpr int kMaxEnergies = 4096;
-
 __host__ __device__ constexpr int per_meas(int M) { return M + 2; }
 __host__ __device__ constexpr int row_len(int K, int M) { return M + K * per_meas(M); }
-__host__ __device__ constexpr int n_sym(int M) { return M * (M + 1) / 2; }
-// index of element (i, j), i <= j, in the row-major upper triangle
-__host__ __device__ constexpr int sym(int M, int i, int j) { return i * M - i * (i - 1) / 2 + (j - i); }
-
-inline size_t tables_bytes(int K, int M, int n_e) {
-  const size_t b = sizeof(double) * (kHeader + (size_t)n_e * row_len(K, M)) + sizeof(int) * (size_t)n_e;
-  return (b + 15) & ~(size_t)15;
-}
-
-__device__ __forceinline__ double load_count(const void* p, int is_f64, int64_t i) {
-  return is_f64 ? reinterpret_cast<const double*>(p)[i] : (double)reinterpret_cast<const float*>(p)[i];
-}
 
 // One block.  Thread 0 lists the energies that some measurement weights in i0 or i0v (a zero weight contributes exactly 0 to
 // every sum: the attenuation factor is finite thanks to the clip), the block then writes their rows.  Row of energy e:
@@ -63,18 +47,8 @@ __global__ __launch_bounds__(kBlock) void gn_cov_tables_kernel(const double* __r
   const int R = row_len(K, M), P = per_meas(M);
   double* __restrict__ tab = ws + kHeader;
   int* __restrict__ perm = reinterpret_cast<int*>(tab + (size_t)n_e * R);
-  if (threadIdx.x == 0) {
-    int n = 0;
-    for (int e = 0; e < n_e; ++e) {
-      bool any = false;
-      for (int k = 0; k < K; ++k)      // NaN counts as a weight
-        any = any || !(i0[(size_t)k * n_e + e] == 0.0) || !(i0v[(size_t)k * n_e + e] == 0.0);
-      if (any) perm[n++] = e;
-    }
-    s_used = n;
-    ws[0] = (double)n;
-    for (int j = 1; j < kHeader; ++j) ws[j] = 0.0;
-  }
+  if (threadIdx.x == 0)
+    s_used = list_energies(K, n_e, [&](size_t i) { return is_weight(i0[i]) || is_weight(i0v[i]); }, perm, ws);
   __syncthreads();
   const int n_used = s_used;
   for (int j = threadIdx.x; j < n_used; j += blockDim.x) {
@@ -98,24 +72,10 @@ __global__ __launch_bounds__(kBlock) void gn_cov_tables_kernel(const double* __r
 // inv[sym] = the inverse of the symmetric matrix h[sym], closed form; a singular or non-finite h leaves inf / NaN
 template <int M>
 __device__ __forceinline__ void sym_inverse(const double (&h)[n_sym(M)], double (&inv)[n_sym(M)]) {
-  if constexpr (M == 2) {
-    const double h00 = h[0], h01 = h[1], h11 = h[2];
-    const double inv_det = rcp_f64(h00 * h11 - h01 * h01);
-    inv[0] = h11 * inv_det;
-    inv[1] = -h01 * inv_det;
-    inv[2] = h00 * inv_det;
-  } else {
-    const double h00 = h[0], h01 = h[1], h02 = h[2], h11 = h[3], h12 = h[4], h22 = h[5];
-    const double c00 = h11 * h22 - h12 * h12, c01 = h02 * h12 - h01 * h22, c02 = h01 * h12 - h02 * h11;
-    const double c11 = h00 * h22 - h02 * h02, c12 = h01 * h02 - h00 * h12, c22 = h00 * h11 - h01 * h01;
-    const double inv_det = rcp_f64((h00 * c00 + h01 * c01) + h02 * c02);
-    inv[0] = c00 * inv_det;
-    inv[1] = c01 * inv_det;
-    inv[2] = c02 * inv_det;
-    inv[3] = c11 * inv_det;
-    inv[4] = c12 * inv_det;
-    inv[5] = c22 * inv_det;
-  }
+  double c[n_sym(M)];
+  const double inv_det = sym_adjugate<M>(h, c);
+#pragma unroll
+  for (int t = 0; t < n_sym(M); ++t) inv[t] = c[t] * inv_det;
 }
 
 // out[sym] = sum_k w_k G_km G_kn for m <= n; G_km = acc[k][2 + m]
@@ -276,42 +236,24 @@ using namespace dexct;
 extern "C" {
 
 int64_t dexct_gn_cov_workspace_bytes(int32_t n_meas, int32_t n_mats, int32_t n_energies) {
-  if (n_mats < 2 || n_mats > DEXCT_GN_MAX_MATS || n_meas < n_mats || n_meas > DEXCT_GN_MAX_MEAS) return 0;
-  if (n_energies <= 0 || n_energies > kMaxEnergies) return 0;
-  return (int64_t)tables_bytes(n_meas, n_mats, n_energies);
+  return workspace_bytes(n_meas, n_mats, n_energies, row_len);
 }
 
 int dexct_gn_covariance(const double* a, int64_t n_pix, int32_t n_meas, int32_t n_mats, const double* i0, const double* i0v,
                         const double* mus, int32_t n_energies, int32_t kind, const void* mask_g, int32_t g_is_f64,
                         const double* mask_max, double mask_frac, double* out_cov, void* workspace, void* stream) {
-  if (!a || !i0 || !i0v || !mus || !out_cov || !workspace) return DEXCT_EINVAL;
-  if (n_pix < 0 || n_energies <= 0) return DEXCT_EINVAL;
-  if (kind != DEXCT_COV_ESTIMATOR && kind != DEXCT_COV_CRLB) return DEXCT_EINVAL;
-  if (g_is_f64 != 0 && g_is_f64 != 1) return DEXCT_EINVAL;
-  if (n_meas < 2 || n_mats < 2 || n_mats > n_meas) return DEXCT_EINVAL;
-  if (n_meas > DEXCT_GN_MAX_MEAS || n_mats > DEXCT_GN_MAX_MATS) return DEXCT_ERANGE;
-  if (mask_g && !mask_max) return DEXCT_EINVAL;
-  if (reinterpret_cast<uintptr_t>(a) & 7u) return DEXCT_EINVAL;
-  if (reinterpret_cast<uintptr_t>(out_cov) & 7u) return DEXCT_EINVAL;
-  if (reinterpret_cast<uintptr_t>(workspace) & 7u) return DEXCT_EINVAL;
-  if (mask_g && (reinterpret_cast<uintptr_t>(mask_g) & (g_is_f64 ? 7u : 3u))) return DEXCT_EINVAL;
-  if (n_energies > kMaxEnergies) return DEXCT_ERANGE;
-  const int64_t nblk = (n_pix + kBlock - 1) / kBlock;
-  if (nblk > 0x7FFFFFFFll) return DEXCT_ERANGE;
+  const bool kind_ok = kind == DEXCT_COV_ESTIMATOR || kind == DEXCT_COV_CRLB;
+  const int bad = check_args(a && i0 && i0v && mus && out_cov && workspace && kind_ok, n_pix, n_meas, n_mats, n_energies, g_is_f64,
+                             !(mask_g && !mask_max), mask_g, a, out_cov, workspace);
+  if (bad) return bad;
   if (n_pix == 0) return DEXCT_OK;
   hipStream_t st = as_stream(stream);
   double* ws = reinterpret_cast<double*>(workspace);
   hipLaunchKernelGGL(gn_cov_tables_kernel, dim3(1), dim3(kBlock), 0, st, i0, i0v, mus, n_meas, n_mats, n_energies, ws);
   DEXCT_LAUNCH_CHECK();
-#define DEXCT_GN_COV_CASE(K, M) \
-  if (n_meas == K && n_mats == M) return launch<K, M>(kind, a, n_pix, ws, mask_g, g_is_f64, mask_max, mask_frac, out_cov, st)
-  DEXCT_GN_COV_CASE(2, 2);
-  DEXCT_GN_COV_CASE(3, 2);
-  DEXCT_GN_COV_CASE(4, 2);
-  DEXCT_GN_COV_CASE(3, 3);
-  DEXCT_GN_COV_CASE(4, 3);
-#undef DEXCT_GN_COV_CASE
-  return DEXCT_EINVAL;
+  return for_shape(n_meas, n_mats, [&](auto K, auto M) {
+    return launch<decltype(K)::value, decltype(M)::value>(kind, a, n_pix, ws, mask_g, g_is_f64, mask_max, mask_frac, out_cov, st);
+  });
 }
 
 int dexct_cov_quadform(const double* cov, int64_t n_pix, int32_t n_mats, const double* u, double* out, void* stream) {
