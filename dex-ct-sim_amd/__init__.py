@@ -10,7 +10,8 @@ from .system import (FanBeamGeometry, Material, Phantom, ScannerGeometry, Spectr
 
 __all__ = ['FanBeamGeometry', 'ScannerGeometry', 'VoxelPhantom', 'Phantom', 'xRaySpectrum', 'Spectrum', 'Material',
            'read_parameter_file', 'get_sino', 'get_sinos', 'get_recon', 'get_basismat_sinos', 'do_matdecomp_gn', 'energy_bins',
-           'get_basismat_sinos_multi', 'decomposition_tables_multi', 'get_basismat_covariance', 'get_recon_covariance']
+           'get_basismat_sinos_multi', 'decomposition_tables_multi', 'get_basismat_covariance', 'get_recon_covariance',
+           'get_basismat_recon']
 
 
 def __getattr__(name):
@@ -18,7 +19,7 @@ def __getattr__(name):
     if name in ('get_sino', 'get_sinos', 'Projector'):
         from . import forward_project
         return getattr(forward_project, name)
-    if name in ('get_recon', 'get_recon_covariance', 'recon_covariance_device'):
+    if name in ('get_recon', 'get_recon_covariance', 'recon_covariance_device', 'get_basismat_recon'):
         from . import back_project
         return getattr(back_project, name)
     if name in ('make_vmi', 'measure_roi', 'vmi_roi_sweep', 'vmi_rmse_sweep', 'vmi_variance', 'vmi_noise_sweep', 'vmi_noise_map'):

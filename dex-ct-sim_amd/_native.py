@@ -18,6 +18,7 @@ SYMBOLS = ['dexct_strerror', 'dexct_abi_version', 'dexct_last_hip_error', 'dexct
            'dexct_bhc_linearize', 'dexct_image_project', 'dexct_image_backproject', 'dexct_sirt_residual', 'dexct_sirt_update',
            'dexct_gn_reduced_rows', 'dexct_gn_decompose_multi', 'dexct_gn_covariance', 'dexct_cov_quadform',
            'dexct_fbp_var_filter', 'dexct_fbp_var_backproject', 'dexct_fdk_var_backproject',
+           'dexct_cov_precision', 'dexct_pwls_majorizer', 'dexct_pwls_residual', 'dexct_pwls_update',
            'dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes', 'dexct_gn_multi_workspace_bytes', 'dexct_gn_cov_workspace_bytes']
 # the size queries return int64_t; dexct_strerror a string; every other entry point an int status
 SIZE_QUERIES = ['dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes', 'dexct_gn_multi_workspace_bytes',
@@ -149,6 +150,10 @@ def load():
     lib.dexct_image_backproject.argtypes = [C.POINTER(FanGeom), vp, i32, i32, i32, vp, vp, vp, i32, vp]
     lib.dexct_sirt_residual.argtypes = [vp, vp, vp, i32, i32, i64, vp, vp, vp]
     lib.dexct_sirt_update.argtypes = [vp, vp, vp, i64, f64, i32, vp]
+    lib.dexct_cov_precision.argtypes = [vp, i64, i32, f64, vp, vp]
+    lib.dexct_pwls_majorizer.argtypes = [vp, vp, i64, i32, vp, vp]
+    lib.dexct_pwls_residual.argtypes = [vp, vp, vp, vp, i64, i32, i32, i32, i64, vp, vp, vp]
+    lib.dexct_pwls_update.argtypes = [vp, vp, vp, i32, i32, i32, i32, f64, C.POINTER(f64), C.POINTER(f64), i32, vp, vp, vp]
     lib.dexct_label_moments.argtypes = [vp, vp, vp, i64, i32, vp, vp]
     lib.dexct_sino_allgather.argtypes = [vp, vp, i64, vp, vp]
     lib.dexct_sino_gather.argtypes = [vp, vp, C.POINTER(i64), C.POINTER(i64), i32, i32, i32, vp, vp]

@@ -181,7 +181,7 @@ def _recon_iterative(sino_d, ct, N_matrix, FOV, ramp, window, bhc, method, n_ite
 
 
 def get_recon(sino, ct, spec, N_matrix, FOV, ramp, window=None, slices=None, bhc=None, method='fbp', n_iters=20, n_subsets=1,
-              relax=1.0, init='fbp', nonneg=True, history=None):
+              relax=1.0, init='fbp', nonneg=True, history=None, weights=None, beta=0.0, delta=1e-3):
     """Drop-in for ``recon_raw, recon_HU = get_recon(sino, ct, spec, N_matrix, FOV, ramp)`` (main.py:134).
     ``window``: apodisation of the ramp (WINDOWS; default ``DEXCT_FBP_WINDOW`` or the plain band-limited ramp).
     Cone-beam sinograms ([N_proj, N_rows, N_channels] of a ``cone=True`` scanner) are reconstructed with Feldkamp's
@@ -195,8 +195,33 @@ def get_recon(sino, ct, spec, N_matrix, FOV, ramp, window=None, slices=None, bhc
     from zero (``'zero'``), clamped at 0 after every update if ``nonneg``; ``history``: a list that receives the weighted
     residual norm before each iteration.  Fan and stacked fan only.  The warning about non-finite values, ``bhc`` and the HU
     formula are those of the FBP path.  A short scan needs no Parker weights here: the iteration solves A x = b for the views
-    there are, and a ray measured twice simply enters twice (the weights only serve init='fbp')."""
-    if method != 'fbp':
+    there are, and a ray measured twice simply enters twice (the weights only serve init='fbp').
+    ``method='pwls'``: penalised weighted least squares, the single-channel case of get_basismat_recon - ``weights`` (needed) is
+    the inverse variance of every sinogram value, of the sinogram's shape and >= 0 (0: the ray is ignored), ``beta`` and
+    ``delta`` the strength and the threshold of the Huber penalty; ``n_iters``, ``n_subsets``, ``init``, ``nonneg`` and
+    ``history`` (here: the objective before each iteration) as above, ``relax`` is not used.  Non-finite sinogram values get
+    the weight 0.  Like ``sino``, ``weights`` is a host array (device tensors: iterative.pwls); ``slices`` belongs to the cone
+    branch and is refused here; single process, as get_basismat_recon."""
+    pwls = method == 'pwls'
+    if pwls:
+        from . import iterative
+        n_subsets, beta, delta = iterative.check_pwls_options(ct, 1, n_iters, n_subsets, beta, delta, init, FOV)
+        if weights is None:
+            raise ValueError("method='pwls' needs weights: the inverse variance of every sinogram value")
+        if slices is not None:
+            raise ValueError("slices belong to the cone-beam FBP: method='pwls' reconstructs the rows of the sinogram")
+        if getattr(weights, 'is_cuda', False) or getattr(sino, 'is_cuda', False):
+            raise ValueError('get_recon takes host arrays: device tensors go to get_basismat_recon or iterative.pwls')
+        if tuple(np.shape(weights)) != tuple(np.shape(sino)):
+            raise ValueError(f'weights {tuple(np.shape(weights))} do not have the shape of the sinogram {tuple(np.shape(sino))}')
+        if np.ndim(sino) not in (2, 3) or np.shape(sino)[0] != ct.N_proj or np.shape(sino)[-1] != ct.N_channels:
+            raise ValueError(f'sinogram {tuple(np.shape(sino))} does not match the scanner ({ct.N_proj} x {ct.N_channels})')
+        from . import _shard
+        if _shard.world()[1] > 1:
+            raise NotImplementedError("get_recon(method='pwls') runs on a single process")
+    elif weights is not None:
+        raise ValueError(f"weights belong to method='pwls', not to {method!r}")
+    elif method != 'fbp':
         from . import iterative
         iterative.check_options(method, ct, n_iters, n_subsets, relax, init, FOV)
     dev = device()
@@ -207,18 +232,104 @@ def get_recon(sino, ct, spec, N_matrix, FOV, ramp, window=None, slices=None, bhc
         # detector line in the filter and over the whole image in the back-projection
         import warnings
         warnings.warn(f'get_recon: {bad} non-finite sinogram value(s) set to 0 before filtering', RuntimeWarning)
+        dead = ~torch.isfinite(sino_d) if pwls else None
         sino_d = torch.nan_to_num(sino_d, nan=0.0, posinf=0.0, neginf=0.0)
     if bhc is not None:
         from . import bhc as bhc_mod
         table = bhc if isinstance(bhc, bhc_mod.LinearizationTable) else bhc_mod.linearization_table(ct, spec, bhc)
         bhc_mod.linearize_device(sino_d, table, out=sino_d)         # sino_d is this call's own copy
-    if method != 'fbp':
+    if pwls:
+        weights_d = to_dev(np.asarray(weights, dtype=np.float32), torch.float32, dev)
+        if not bool((torch.isfinite(weights_d) & (weights_d >= 0)).all().item()):
+            raise ValueError('weights must be finite and >= 0')
+        if bad:
+            weights_d[dead] = 0.0
+        three_d = sino_d.dim() == 3
+        shape = (1, ct.N_proj, sino_d.shape[1] if three_d else 1, ct.N_channels)
+        img = _recon_pwls(sino_d.reshape(shape), weights_d.reshape(shape), ct, N_matrix, FOV, ramp, window, beta, delta, n_iters,
+                          n_subsets, init, nonneg, history)[0]
+        raw = (img if three_d else img[0]).cpu().numpy()
+    elif method != 'fbp':
         raw = recon_device(sino_d, ct, N_matrix, FOV, ramp, window, None, None, method, n_iters, n_subsets, relax, init, nonneg,
                            history).cpu().numpy()
     else:
         raw = recon_device(sino_d, ct, N_matrix, FOV, ramp, window, slices).cpu().numpy()
     mu_w = water_mu(ct, spec)
     return raw, (1000.0 * (raw - mu_w) / mu_w).astype(np.float32)
+
+
+def _recon_pwls(sinos_d, weights_d, ct, N_matrix, FOV, ramp, window, beta, delta, n_iters, n_subsets, init, nonneg, history):
+    """iterative.pwls of sinograms [K, N_proj, n_rows, N_channels] with the packed weights [T, N_proj, n_rows, N_channels]
+    (device float32), every channel started from its FBP image (``init='fbp'``) or from zero -> images [K, n_rows, N, N]."""
+    from . import iterative
+    K, _, n_rows, _ = sinos_d.shape
+    proj = iterative.ImageProjector(ct, N_matrix, FOV, n_slices=n_rows)
+    x0 = None
+    if init == 'fbp':
+        x0 = torch.stack([recon_device(sinos_d[k], ct, N_matrix, FOV, ramp, window) for k in range(K)])
+    return iterative.pwls(sinos_d, weights_d, proj, n_iters, n_subsets, beta, delta, x0=x0, nonneg=nonneg, history=history)
+
+
+def get_basismat_recon(basis_sinos, cov_sino, ct, N_matrix, FOV, ramp, beta, delta, n_iters=20, n_subsets=1, init='fbp',
+                       nonneg=False, w_fill=0.0, history=None, window=None):
+    """Joint statistical reconstruction of the K = 1 .. 3 basis-material images from the basis sinograms and their per-ray noise
+    covariance: penalised weighted least squares with the inverse covariance as the weight and a Huber penalty (iterative.pwls,
+    which states the objective and the iteration).
+
+    basis_sinos: K sinograms, each [N_proj, N_channels] or [N_proj, N_rows, N_channels] - what get_basismat_sinos returns;
+    cov_sino: exactly what matdecomp.get_basismat_covariance returns for them, [N_proj, (N_rows,) N_channels, T] with T =
+    K (K + 1) / 2 (var(m1), cov(m1, m2), var(m2) for two).  ``beta``, ``delta``: strength and threshold [the images' unit] of the
+    Huber penalty, a scalar or one value per channel; ``n_iters`` iterations over ``n_subsets`` ordered subsets of the views,
+    started from the FBP image of every channel (``init='fbp'``, with ``ramp`` and ``window``) or from zero; ``nonneg`` clamps at 0
+    (off: basis images may be negative).  A ray whose covariance is not finite and positive definite - the exact zeros of an
+    air-masked pixel, a diverged decomposition - weighs ``w_fill`` on the diagonal and 0 off it (0: the ray is ignored).
+    Non-finite sinogram values are set to 0 with a RuntimeWarning, as in get_recon, and their rays get ``w_fill`` too.
+    ``history``: a list that receives the objective before each iteration.  Returns a tuple of K images [N_matrix, N_matrix]
+    or [N_rows, N_matrix, N_matrix], float32: NumPy arrays, or device tensors if the sinograms were device tensors.  Fan and
+    stacked fan only; single process."""
+    from . import iterative
+    sinos = list(basis_sinos)
+    K = len(sinos)
+    n_subsets, beta, delta = iterative.check_pwls_options(ct, K, n_iters, n_subsets, beta, delta, init, FOV)
+    shapes = [tuple(t.shape) if isinstance(t, torch.Tensor) else np.shape(t) for t in sinos]
+    shape = shapes[0]
+    if any(sh != shape for sh in shapes):
+        raise ValueError(f'the basis sinograms differ in shape: {shapes}')
+    if len(shape) not in (2, 3) or shape[0] != ct.N_proj or shape[-1] != ct.N_channels:
+        raise ValueError(f'sinogram {shape} does not match the scanner ({ct.N_proj} x {ct.N_channels})')
+    T = K * (K + 1) // 2
+    cov_shape = tuple(cov_sino.shape) if isinstance(cov_sino, torch.Tensor) else np.shape(cov_sino)
+    if cov_shape != shape + (T,):
+        raise ValueError(f'covariance sinogram {cov_shape}: {shape + (T,)} wanted for {K} sinogram(s) of shape {shape}')
+    if not (float(w_fill) >= 0.0 and np.isfinite(float(w_fill))):
+        raise ValueError(f'w_fill = {w_fill}: a finite value >= 0 wanted')
+    window = window or default_window()
+    if window not in WINDOWS:
+        raise ValueError(f'unknown filter window {window!r}; choose from {sorted(WINDOWS)}')
+    _short_scan(ct)
+    from . import _shard
+    if _shard.world()[1] > 1:
+        raise NotImplementedError('get_basismat_recon runs on a single process')
+    tensors_in = all(isinstance(t, torch.Tensor) for t in sinos)
+    dev = device()
+    three_d = len(shape) == 3
+    full = (ct.N_proj, shape[1] if three_d else 1, ct.N_channels)
+    s = torch.stack([to_dev(t if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float32), torch.float32, dev).reshape(full)
+                     for t in sinos])
+    cov_d = to_dev(cov_sino if isinstance(cov_sino, torch.Tensor) else np.asarray(cov_sino, dtype=np.float64), torch.float64, dev)
+    cov_d = cov_d.reshape(full + (T,))
+    finite = torch.isfinite(s)
+    bad = int((~finite).sum().item())
+    if bad:
+        import warnings
+        warnings.warn(f'get_basismat_recon: {bad} non-finite sinogram value(s) set to 0 before the reconstruction', RuntimeWarning)
+        s = torch.nan_to_num(s, nan=0.0, posinf=0.0, neginf=0.0)
+        # their rays are unusable: a NaN covariance makes dexct_cov_precision write w_fill (into a copy: cov_sino is the caller's)
+        cov_d = torch.where(finite.all(0)[..., None], cov_d, torch.full_like(cov_d, float('nan')))
+    w = iterative.precision_weights(cov_d, w_fill)
+    imgs = _recon_pwls(s, w, ct, N_matrix, FOV, ramp, window, beta, delta, n_iters, n_subsets, init, nonneg, history)
+    out = tuple(imgs[k] if three_d else imgs[k, 0] for k in range(K))
+    return out if tensors_in else tuple(t.cpu().numpy() for t in out)
 
 
 def _check_cov_sino(shape, ct, window):

@@ -16,8 +16,18 @@ kernels form them with one device function, so <A x, y> = <x, A^T y> up to float
 S = 1 is SIRT (Gilbert 1972; for relax in (0, 2) the R-weighted residual norm never increases), S > 1 is OS-SART (Andersen &
 Kak 1984 with ordered subsets).  Every step is a HIP kernel (dexct_sirt_residual, dexct_sirt_update); torch tensors are the
 device containers.
+
+``pwls`` is the statistical iteration on the same pair: K = 1 .. 3 channels (sinograms b_k, images x_k) coupled by a symmetric
+K x K weight matrix W_i per ray - the inverse of the covariance of the basis line integrals (``precision_weights``) - and an
+edge-preserving Huber penalty on the in-plane 4-neighbourhood of every image:
+
+    Phi(x) = 1/2 sum_i r_i^T W_i r_i + sum_k beta_k sum_pairs psi_(delta_k)(x_kj - x_kn)       r_i = ((A x_k)_i - b_ki)_k
+
+minimised with ordered-subsets separable quadratic surrogates (Erdogan & Fessler 1999); the steps are stated at ``pwls`` and
+are the kernels of csrc/pwls.hip (dexct_pwls_majorizer, dexct_pwls_residual, dexct_pwls_update).
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
@@ -92,6 +102,7 @@ class ImageProjector:
         self.transposed = bool(transposed)
         self.plan = None
         self._row_sums, self._col_sums = None, {}
+        self._pwls_d = None
 
     # ---- device state ---------------------------------------------------------------------------------------------------------
     def _ready(self):
@@ -163,6 +174,11 @@ class ImageProjector:
             'dexct_image_backproject')
         return out
 
+    def forget_weights(self):
+        """Drop the majoriser ``pwls`` keeps for its last weight tensor (it is made again on the next call): needed only after
+        that tensor was overwritten through its raw pointer, which torch does not see."""
+        self._pwls_d = None
+
     def row_sums(self):
         """R = A 1 (the forward kernel applied to an image of ones), cached."""
         if self._row_sums is None:
@@ -222,4 +238,159 @@ def sirt(sino_d, proj, n_iters, n_subsets=1, relax=1.0, x0=None, nonneg=True, hi
                                                 stream_ptr()), 'dexct_sirt_update')
         if history is not None and S == 1:
             history.append(float(np.sqrt(norm2.item())))
+    return x
+
+
+# ---- joint penalised weighted least squares (OS-SQS, Huber) -----------------------------------------------------------------------
+
+PWLS_MAX_CHANNELS = 3
+
+
+def per_channel(value, K, what, positive=False):
+    """A scalar or one value per channel -> K floats; beta >= 0, delta > 0 (``positive``), finite."""
+    v = np.asarray(value, dtype=np.float64).reshape(-1)
+    if v.size == 1:
+        v = np.repeat(v, K)
+    if v.size != K:
+        raise ValueError(f'{what} = {value!r}: a scalar or one value per channel ({K}) wanted')
+    if not np.all(np.isfinite(v)) or (positive and not np.all(v > 0)) or not np.all(v >= 0):
+        raise ValueError(f'{what} = {value!r}: {"positive" if positive else "non-negative"} finite values wanted')
+    return [float(t) for t in v]
+
+
+def check_pwls_options(ct, K, n_iters, n_subsets, beta, delta, init='fbp', FOV=None):
+    """The argument checks of ``get_basismat_recon`` and ``get_recon(..., method='pwls')`` that need no device.  Returns
+    (n_subsets, beta per channel, delta per channel)."""
+    if not 1 <= int(K) <= PWLS_MAX_CHANNELS:
+        raise ValueError(f'{K} channels: the joint reconstruction takes 1 .. {PWLS_MAX_CHANNELS}')
+    if bool(getattr(ct, 'cone', False)):
+        raise ValueError('iterative reconstruction is fan and stacked-fan only: a cone-beam scanner has no matched pair here')
+    if FOV is not None and 0.5 * np.sqrt(2.0) * float(FOV) >= ct.SID:
+        raise ValueError(f'FOV = {FOV} cm: the image grid does not lie strictly inside the source circle (SID = {ct.SID} cm)')
+    if init not in ('fbp', 'zero'):
+        raise ValueError(f"init must be 'fbp' or 'zero', not {init!r}")
+    if int(n_iters) < 1:
+        raise ValueError(f'n_iters = {n_iters}: at least one iteration')
+    if not 1 <= int(n_subsets) <= ct.N_proj:
+        raise ValueError(f'n_subsets = {n_subsets} lies outside 1 .. N_proj = {ct.N_proj}')
+    return int(n_subsets), per_channel(beta, K, 'beta'), per_channel(delta, K, 'delta', positive=True)
+
+
+def channels_of(n_planes):
+    """K of a packed triangle of T = K (K + 1) / 2 planes (ValueError for any other T)."""
+    for K in range(1, PWLS_MAX_CHANNELS + 1):
+        if K * (K + 1) // 2 == int(n_planes):
+            return K
+    raise ValueError(f'{n_planes} planes are no packed triangle of 1 .. {PWLS_MAX_CHANNELS} channels (1, 3 or 6 wanted)')
+
+
+def precision_weights(cov_d, w_fill=0.0):
+    """The per-ray precision matrices of a packed covariance: cov_d, device float64 [..., T] (the layout of
+    matdecomp.gn_covariance_device) -> float32 [T, ...], plane-major, each plane a sinogram (dexct_cov_precision: the float64
+    closed-form inverse rounded once; a ray whose matrix is not finite and positive definite gets ``w_fill`` on the diagonal
+    planes and 0 elsewhere)."""
+    if not (isinstance(cov_d, torch.Tensor) and cov_d.is_cuda and cov_d.dtype == torch.float64):
+        raise ValueError('cov_d must be a float64 device tensor')
+    T = cov_d.shape[-1]
+    K = channels_of(T)
+    if not (float(w_fill) >= 0.0 and np.isfinite(float(w_fill))):
+        raise ValueError(f'w_fill = {w_fill}: a finite value >= 0 wanted')
+    c = cov_d.contiguous()
+    w = torch.empty((T,) + tuple(c.shape[:-1]), dtype=torch.float32, device=c.device)
+    _native.check(_native.load().dexct_cov_precision(ptr(c), c.numel() // T, K, float(w_fill), ptr(w), stream_ptr()),
+                  'dexct_cov_precision')
+    return w
+
+
+def _pwls_majoriser(proj, w, K):
+    """d_k = A^T((sum_l |W_kl|) R) over ALL views, [K, nz, ny, nx]; kept on the projector for the weight tensor it was made
+    from: the same object, unchanged since by torch's count of in-place operations.  A write through the raw pointer (a
+    library call given ``w.data_ptr()``) is invisible to that count: after one, call ``proj.forget_weights()``."""
+    hit = proj._pwls_d
+    if hit is not None and hit[0]() is w and hit[1] == w._version:
+        return hit[2]
+    m = torch.empty((K,) + proj.sino_shape, dtype=torch.float32, device=proj.dev)
+    _native.check(proj.lib.dexct_pwls_majorizer(ptr(w), ptr(proj.row_sums()), m[0].numel(), K, ptr(m), stream_ptr()),
+                  'dexct_pwls_majorizer')
+    d = torch.empty((K,) + proj.image_shape, dtype=torch.float32, device=proj.dev)
+    for k in range(K):
+        proj.adjoint(m[k], out=d[k])
+    proj._pwls_d = (weakref.ref(w), w._version, d)
+    return d
+
+
+def pwls(sinos_d, weights_d, proj, n_iters, n_subsets=1, beta=0.0, delta=1e-3, x0=None, nonneg=False, history=None):
+    """Joint penalised weighted least squares of K = 1 .. 3 channels, ``n_iters`` passes over the ``n_subsets`` ordered
+    subsets (subset s = the views congruent to s modulo S, as in ``sirt``).
+
+    sinos_d: device float32 [K, n_views, n_rows, n_channels] (or a sequence of K sinograms); weights_d: device float32
+    [T, n_views, n_rows, n_channels], the packed upper triangle of the symmetric positive semi-definite W_i
+    (``precision_weights``); ``beta``, ``delta``: a scalar or one value per channel; x0: start images [K, nz, ny, nx] (default
+    zeros; not modified).  Per subset, with R = A 1:
+
+        q_k  = sum_l W_kl (A_s x_l - b_l)                  on the lines of the subset, 0 where R = 0
+        g_k  = S A_s^T q_k
+        d_k  = A^T((sum_l |W_kl|) R)                       once, over ALL views
+        p_kj = beta_k sum_(n in N(j)) clip(x_kj - x_kn, +-delta_k)
+        c_kj = 2 beta_k sum_(n in N(j)) min(1, delta_k / |x_kj - x_kn|)
+        x_kj <- x_kj - (g_kj + p_kj) / (d_kj + c_kj)       where the denominator > 0 (other pixels stay); max(., 0) if nonneg
+
+    a Jacobi step between two image buffers.  d majorises the data Hessian for every symmetric positive semi-definite W because
+    a_ij >= 0 (row (k, j) of |H| 1 is d_kj), so with one subset Phi never increases.  The K channels go through the
+    projector pair one call each.  ``history``: a list that receives Phi of the images BEFORE each iteration, data term (over
+    the rays with R > 0) plus penalty, summed in float64 on the device (one host synchronisation per iteration; with more than
+    one subset also one full forward projection per iteration, as ``sirt``).  Returns the images [K, nz, ny, nx]."""
+    n_iters, S = int(n_iters), int(n_subsets)
+    if n_iters < 1 or not 1 <= S <= proj.n_views:
+        raise ValueError(f'n_iters = {n_iters}, n_subsets = {S}: n_iters >= 1 and 1 <= n_subsets <= {proj.n_views} wanted')
+    if not isinstance(sinos_d, torch.Tensor):
+        sinos_d = torch.stack([t.reshape(proj.sino_shape) for t in sinos_d])
+    K = int(sinos_d.shape[0]) if sinos_d.dim() == len(proj.sino_shape) + 1 else 0
+    if not 1 <= K <= PWLS_MAX_CHANNELS:
+        raise ValueError(f'sinograms {tuple(sinos_d.shape)}: [K, n_views, n_rows, n_channels] with K = 1 .. {PWLS_MAX_CHANNELS} wanted')
+    T = K * (K + 1) // 2
+    betas, deltas = per_channel(beta, K, 'beta'), per_channel(delta, K, 'delta', positive=True)
+    proj._ready()
+    lib, dev = proj.lib, proj.dev
+    b = proj._tensor(sinos_d, (K,) + proj.sino_shape, 'sinograms')
+    w = proj._tensor(weights_d, (T,) + proj.sino_shape, 'weights')
+    x = torch.zeros((K,) + proj.image_shape, dtype=torch.float32, device=dev) if x0 is None else \
+        proj._tensor(x0, (K,) + proj.image_shape, 'x0').clone()
+    y = torch.empty_like(x)
+    R = proj.row_sums()
+    d = _pwls_majoriser(proj, w, K)
+    ax = torch.zeros((K,) + proj.sino_shape, dtype=torch.float32, device=dev)
+    g = torch.empty((K,) + proj.image_shape, dtype=torch.float32, device=dev)
+    phi = torch.zeros(2, dtype=torch.float64, device=dev) if history is not None else None      # data term, penalty
+    line = proj.n_rows * proj.n_channels
+    n_views, plane = proj.n_views, proj.n_views * line
+    beta_c, delta_c = (C.c_double * K)(*betas), (C.c_double * K)(*deltas)
+    data_ptr = None if phi is None else phi.data_ptr()
+    pen_ptr = None if phi is None else phi.data_ptr() + 8
+
+    def residual(s, step, q, objective):
+        off = 4 * s * line
+        _native.check(lib.dexct_pwls_residual(b.data_ptr() + off, ax.data_ptr() + off, w.data_ptr() + off, R.data_ptr() + off, plane,
+                                              K, n_views - s, step, line, None if q is None else q.data_ptr() + off, objective,
+                                              stream_ptr()), 'dexct_pwls_residual')
+
+    for _ in range(n_iters):
+        if history is not None and S > 1:                  # (with one subset the iteration's own residual is the one wanted)
+            for k in range(K):
+                proj.forward(x[k], out=ax[k])
+            residual(0, 1, None, data_ptr)
+        for s in range(S):
+            views = (s, n_views, S)
+            for k in range(K):
+                proj.forward(x[k], views=views, out=ax[k])
+            residual(s, S, ax, data_ptr if S == 1 else None)
+            for k in range(K):
+                proj.adjoint(ax[k], views=views, out=g[k])
+            _native.check(lib.dexct_pwls_update(ptr(x), ptr(g), ptr(d), K, proj.nz, proj.ny, proj.nx, float(S), beta_c, delta_c,
+                                                int(bool(nonneg)), ptr(y), pen_ptr if s == 0 else None, stream_ptr()),
+                          'dexct_pwls_update')
+            x, y = y, x
+            if history is not None and s == 0:
+                data, penalty = phi.tolist()
+                history.append(data + penalty)
     return x

@@ -11,6 +11,9 @@ for every run in the parameter file, for every dual-energy spectrum pair:
      beam-hardening-corrected images of every log sinogram, ``recon_{water,bone}BHC_{raw,HU}_float32.bin`` (the files
      the reference's plots.py:184-195 reads; basis-material sinograms are linear in thickness already and get none);
      ``--recon sirt`` reconstructs all of them iteratively (SIRT / OS-SART, iterative.py) instead of by FBP.
+     ``--recon pwls`` (needs ``--covariance``) reconstructs the two basis-material sinograms JOINTLY, weighted with the
+     inverse of their predicted covariance and with a Huber penalty (back_project.get_basismat_recon; ``--recon-beta``,
+     ``--recon-delta``), into the same ``mat{1,2}_recon_float32.bin``; the single-energy images stay FBP.
   4. with ``--covariance``: the predicted noise covariance of the two basis-material sinograms per detector pixel
      (matdecomp.get_basismat_covariance at the decomposed line integrals, for the doses of the pair), written next to them as
      ``cov11_sino_float32.bin``, ``cov12_sino_float32.bin``, ``cov22_sino_float32.bin``; air pixels hold 0 like the sinograms.
@@ -36,7 +39,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 
 import dex_ct_sim_amd as dx  # noqa: E402
-from dex_ct_sim_amd.back_project import get_recon, get_recon_covariance  # noqa: E402
+from dex_ct_sim_amd.back_project import get_basismat_recon, get_recon, get_recon_covariance  # noqa: E402
 from dex_ct_sim_amd.forward_project import get_sinos  # noqa: E402
 from dex_ct_sim_amd.matdecomp import get_basismat_covariance, get_basismat_sinos  # noqa: E402
 
@@ -92,11 +95,17 @@ def main(argv=None):
     ap.add_argument('--bhc', nargs='*', default=[], choices=['water', 'bone'],
                     help='also write beam-hardening-corrected reconstructions of every log sinogram, linearised for '
                          'these reference materials (recon_<m>BHC_{raw,HU}_float32.bin beside recon_raw)')
-    ap.add_argument('--recon', default='fbp', choices=['fbp', 'sirt'],
-                    help='reconstruction method: filtered back-projection (default) or SIRT / OS-SART on the matched projector '
-                         'pair, started from the FBP image; the output file names stay the reference\'s')
-    ap.add_argument('--recon-iters', type=int, default=20, help='iterations of --recon sirt')
-    ap.add_argument('--recon-subsets', type=int, default=1, help='ordered subsets of --recon sirt (1: SIRT, more: OS-SART)')
+    ap.add_argument('--recon', default='fbp', choices=['fbp', 'sirt', 'pwls'],
+                    help='reconstruction method: filtered back-projection (default), SIRT / OS-SART on the matched projector '
+                         'pair, started from the FBP image, or pwls: the basis-material images jointly by penalised weighted '
+                         'least squares with the --covariance of the decomposition as the weight (the single-energy images stay '
+                         'FBP); the output file names stay the reference\'s')
+    ap.add_argument('--recon-iters', type=int, default=20, help='iterations of --recon sirt / pwls')
+    ap.add_argument('--recon-subsets', type=int, default=1,
+                    help='ordered subsets of --recon sirt (1: SIRT, more: OS-SART) / pwls')
+    ap.add_argument('--recon-beta', type=float, default=0.0, help='strength of the Huber penalty of --recon pwls (0: none)')
+    ap.add_argument('--recon-delta', type=float, default=1e-3,
+                    help='threshold of the Huber penalty of --recon pwls, in the unit of the basis images')
     ap.add_argument('--covariance', nargs='?', const='estimator', default=None, choices=['estimator', 'crlb'],
                     help='also write the predicted noise covariance of each decomposed pair (cov11 / cov12 / cov22 _sino_float32.bin '
                          'beside mat1_sino): of what the Newton solve returns (estimator, the default) or the Cramer-Rao bound '
@@ -112,7 +121,12 @@ def main(argv=None):
         ap.error('--noise-maps propagates the covariance through the FBP: it needs --recon fbp')
     if args.covariance and int(os.environ.get('WORLD_SIZE', '1')) > 1:
         ap.error('--covariance runs on a single process')
-    recon_kw = {} if args.recon == 'fbp' else dict(method=args.recon, n_iters=args.recon_iters, n_subsets=args.recon_subsets)
+    if args.recon == 'pwls' and not args.covariance:
+        ap.error('--recon pwls weights the reconstruction with the covariance of the decomposition: it needs --covariance')
+    if args.recon == 'pwls' and (args.recon_beta < 0 or not args.recon_delta > 0):
+        ap.error('--recon-beta must be >= 0 and --recon-delta > 0')
+    recon_kw = {} if args.recon in ('fbp', 'pwls') else dict(method=args.recon, n_iters=args.recon_iters,
+                                                             n_subsets=args.recon_subsets)
 
     import torch.distributed as dist
     if int(os.environ.get('WORLD_SIZE', '1')) > 1 and not dist.is_initialized():
@@ -184,10 +198,16 @@ def main(argv=None):
                         cov[..., t].astype(np.float32).tofile(sub_dir + f'{name}_sino_float32.bin')
                 if do_bp:
                     print('Back projecting basis material sinograms!')
-                    for i, matsino in enumerate([matsino1, matsino2]):
+                    if args.recon == 'pwls':
+                        mat_recons = get_basismat_recon((matsino1, matsino2), cov, ct, N_matrix, FOV, ramp, args.recon_beta,
+                                                        args.recon_delta, n_iters=args.recon_iters, n_subsets=args.recon_subsets,
+                                                        window=args.window)
+                    else:
                         # spec is filler (:168); basis-material line integrals may be negative: no clamp at 0
                         mat_kw = dict(recon_kw, nonneg=False) if recon_kw else {}
-                        recon_raw, _ = get_recon(matsino, ct, specs[0], N_matrix, FOV, ramp, window=args.window, **mat_kw)
+                        mat_recons = [get_recon(matsino, ct, specs[0], N_matrix, FOV, ramp, window=args.window, **mat_kw)[0]
+                                      for matsino in (matsino1, matsino2)]
+                    for i, recon_raw in enumerate(mat_recons):
                         recon_raw.astype(np.float32).tofile(sub_dir + f'mat{i + 1}_recon_float32.bin')
                     if args.noise_maps:
                         print('Propagating the noise covariance through the reconstruction!')

@@ -754,6 +754,55 @@ int dexct_sirt_residual(const float* b, const float* ax, const float* row_sum, i
                         int64_t line, float* r, double* norm2, void* stream);
 int dexct_sirt_update(float* x, const float* g, const float* col_sum, int64_t n, double relax, int32_t nonneg, void* stream);
 
+/* The element-wise and stencil steps of the joint penalised weighted least-squares reconstruction (csrc/pwls.hip;
+ * dex-ct-sim_amd/iterative.py, pwls, has the iteration): n_mats = K = 1 .. 3 channels - sinograms b_k and images x_k - coupled by
+ * one symmetric K x K weight matrix W per ray.  A symmetric matrix is packed as its row-major upper triangle, T = K (K + 1) / 2
+ * values: (00), (00, 01, 11), (00, 01, 02, 11, 12, 22) - the order of dexct_gn_covariance.  "Plane-major" below: plane t (or
+ * channel k) of a quantity is one contiguous array of the sinogram's (or image's) size, and the planes follow each other at a
+ * fixed stride.  All sinogram and image values are float32, 4-byte aligned; 16-byte loads and stores are used where every
+ * pointer and stride of a call is a multiple of 16 bytes, single elements otherwise.
+ *   dexct_cov_precision:  w[t*n + p] = (C_p^-1)_t rounded once to float32, for the packed float64 covariances cov[T*p + t]
+ *                         (8-byte aligned) of n rays: the inverse in float64 in closed form - the reciprocal, the 2 x 2 formula,
+ *                         the 3 x 3 adjugate over the determinant.  A ray is USABLE when its T values are finite and every
+ *                         leading principal minor is positive (and finite) and every rounded element of the inverse is finite
+ *                         in float32; any other ray - the exact zeros of an air-masked pixel, inf, NaN, a matrix that is not
+ *                         positive definite, variances so small that a weight leaves the float32 range - gets w_fill on the
+ *                         diagonal planes and 0 on the others.  w_fill >= 0 and finite.  n = 0 launches nothing.
+ *   dexct_pwls_majorizer: m[k*n + p] = (sum_l |w_kl[p]|) * row_sum[p] (float32, summed over l = 0 .. K - 1 in that order), K
+ *                         planes; w: the T planes of dexct_cov_precision at stride n, row_sum: R = A 1.  The adjoints of the K
+ *                         planes are the diagonal majoriser d_k of the data term.  m must not overlap its inputs.  n = 0
+ *                         launches nothing.
+ *   dexct_pwls_residual:  over lines j * line_step < n_lines of `line` values each (the convention of dexct_sirt_residual; the
+ *                         pointers address line 0 of the subset), with r_l = ax_l - b_l:
+ *                           q_k = sum_l w_kl r_l   (float32, l = 0 .. K - 1 in that order)   where row_sum > 0, else 0
+ *                         b, ax, q: K planes at stride `plane` values (plane >= n_lines * line), w: T planes at the same stride,
+ *                         row_sum one plane.  q may be NULL or equal ax (no other overlap).  objective (may be NULL; not both
+ *                         NULL): one device float64, zeroed by the call, receives 1/2 sum r^T W r over the same elements with
+ *                         row_sum > 0, formed in float64 from the float32 inputs (float64 atomics across workgroups).
+ *   dexct_pwls_update:    one Jacobi step of the separable quadratic surrogate on images [nz][ny][nx], K planes of n = nz ny nx
+ *                         values each in x_old, g, d and x_new.  With N(j) the in-plane 4-neighbours of pixel j inside the grid,
+ *                         visited left, right, up (iy - 1), down, and t_n = x_old[k][j] - x_old[k][n] (all float32):
+ *                           p = beta_k * sum_n clip(t_n, +-delta_k)
+ *                           c = (2 beta_k) * sum_n (|t_n| > delta_k ? delta_k / |t_n| : 1)
+ *                           x_new = x_old - (g_scale * g + p) / (d + c)   where d + c > 0, else x_old;  then max(., 0) if nonneg
+ *                         (g_scale > 0, used as float32: the subset count S of an ordered-subsets gradient S A_s^T q, 1 without).
+ *                         Every value of x_new is written.  beta, delta: HOST arrays of K float64, used rounded to float32;
+ *                         beta >= 0, delta > 0, finite.  x_new must not overlap x_old (DEXCT_EINVAL).  penalty (may be NULL):
+ *                         one device float64, zeroed by the call, receives sum_k beta_k sum_pairs psi_(delta_k)(t) of the OLD
+ *                         images in float64 - psi(t) = t^2 / 2 for |t| <= delta, delta |t| - delta^2 / 2 beyond; the pairs are
+ *                         (j, right neighbour) and (j, neighbour below), each once, never across slices.  A pixel without a
+ *                         neighbour (nx = ny = 1) has p = c = 0.
+ * DEXCT_EINVAL for null pointers, n_mats outside 1 .. 3, negative or non-finite w_fill, negative n, n_lines <= 0, line_step < 1,
+ * line <= 0, plane < n_lines * line, non-positive grid sizes, a beta, delta or g_scale outside its range and overlapping x_old / x_new;
+ * DEXCT_ERANGE for more than 2^40 values per plane.  Every argument error is returned before the first launch.  No allocation,
+ * no synchronisation, no environment variable. */
+int dexct_cov_precision(const double* cov, int64_t n, int32_t n_mats, double w_fill, float* w, void* stream);
+int dexct_pwls_majorizer(const float* w, const float* row_sum, int64_t n, int32_t n_mats, float* m, void* stream);
+int dexct_pwls_residual(const float* b, const float* ax, const float* w, const float* row_sum, int64_t plane, int32_t n_mats,
+                        int32_t n_lines, int32_t line_step, int64_t line, float* q, double* objective, void* stream);
+int dexct_pwls_update(const float* x_old, const float* g, const float* d, int32_t n_mats, int32_t nz, int32_t ny, int32_t nx,
+                      double g_scale, const double* beta, const double* delta, int32_t nonneg, float* x_new, double* penalty, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
