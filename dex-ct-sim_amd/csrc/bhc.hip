@@ -13,6 +13,8 @@
 namespace dexct {
 
 constexpr int kBhcBlock = 1024;
+// workgroups per CU, the grid cap; tests/grid_caps.py holds its value, tests/test_gpu_grid_passes.py runs past it
+constexpr int kBhcGroupsPerCu = 2;
 
 // The table's cells: per sign of p a run of nodes in a = |p|, a linear run of C = 2^K cells over [0, 2^E] and then C cells
 // per octave [2^(E+o), 2^(E+o+1)), o < n_oct (the layout of float32 itself: the exponent bits give the octave, the top K
@@ -150,10 +152,9 @@ extern "C" int dexct_bhc_linearize(const float* p, int64_t n, const float* table
   if (head > n) head = n;
   // resident workgroups only: two 1024-lane groups fill a CU (32 waves), and a full 64 KiB table still lets both in
   const size_t lds = (size_t)n_nodes * sizeof(float2);
-  const int per_cu = 2;
   const int64_t per_block = (int64_t)kBhcBlock * (vector ? 8 : 1);
   int64_t nb = (n + per_block - 1) / per_block;
-  if (nb > (int64_t)n_cu * per_cu) nb = (int64_t)n_cu * per_cu;
+  if (nb > (int64_t)n_cu * kBhcGroupsPerCu) nb = (int64_t)n_cu * kBhcGroupsPerCu;
   DEXCT_ALLOW_LDS(bhc_linearize_kernel, lds);
   hipLaunchKernelGGL(bhc_linearize_kernel, dim3((unsigned)nb), dim3(kBhcBlock), lds, as_stream(stream), p, n,
                      reinterpret_cast<const float2*>(table), n_nodes, g, out, head, vector);

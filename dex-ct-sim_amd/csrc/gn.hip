@@ -1604,6 +1604,9 @@ __global__ __launch_bounds__(256) void mask_kernel(const void* __restrict__ g1, 
 
 __global__ void max_init_kernel(double* out) { *out = -__builtin_huge_val(); }
 
+// the grid cap of max_kernel; tests/grid_caps.py holds its value, tests/test_gpu_bounds.py (test_apply_mask_and_reduce_max) runs past it
+constexpr int kReduceMaxBlocks = 2048;
+
 // NaN-propagating, like np.max (matdecomp.py:195-196): one NaN count makes the maximum NaN, every comparison
 // `g >= thresh * NaN` is then false and NO pixel is masked - exactly what the reference does with such a sinogram.
 __device__ __forceinline__ double nanmax(double m, double v) {
@@ -1969,7 +1972,7 @@ int dexct_reduce_max(const void* g1, int32_t g_is_f64, int64_t n_pix, double* ou
   hipLaunchKernelGGL(max_init_kernel, dim3(1), dim3(1), 0, st, out_max);
   DEXCT_LAUNCH_CHECK();
   int64_t nblk = (n_pix + 255) / 256;
-  if (nblk > 2048) nblk = 2048;
+  if (nblk > kReduceMaxBlocks) nblk = kReduceMaxBlocks;
   hipLaunchKernelGGL(max_kernel, dim3((unsigned)nblk), dim3(256), 0, st, g1, g_is_f64, n_pix, out_max);
   DEXCT_LAUNCH_CHECK();
   return DEXCT_OK;

@@ -159,10 +159,14 @@ __global__ __launch_bounds__(256) void sirt_residual_kernel(const float* __restr
     const int64_t k = i / line;
     const int64_t o = k * step * line + (i - k * line);
     const float R = row_sum[o];
-    const float d = b[o] - ax[o];
+    const float bo = b[o], ao = ax[o];
+    const float d = bo - ao;
     const bool hit = R > 0.0f;                 // a ray with R = 0 has missed the grid
     if (r) r[o] = hit ? d / R : 0.0f;
-    if (norm2 && hit) acc += (double)d * (double)d / (double)R;
+    if (norm2 && hit) {                        // from the float32 inputs in float64, like the objective of pwls_residual_kernel:
+      const double dd = (double)bo - (double)ao;   // the float32 d would leave its rounding (2^-24 per term) in the sum
+      acc += dd * dd / (double)R;
+    }
   }
   if (!norm2) return;
 #pragma unroll
@@ -199,9 +203,12 @@ static int check_pair(const dexct_fan_geom* g, const void* plan, int view_begin,
   return DEXCT_OK;
 }
 
+// the grid cap of the two SIRT steps; tests/grid_caps.py holds its value, tests/test_gpu_grid_passes.py runs past it
+constexpr int kElementwiseMaxBlocks = 4096;
+
 static int64_t elementwise_blocks(int64_t n) {
   int64_t nb = (n + 255) / 256;
-  return nb < 1 ? 1 : (nb > 4096 ? 4096 : nb);
+  return nb < 1 ? 1 : (nb > kElementwiseMaxBlocks ? kElementwiseMaxBlocks : nb);
 }
 
 }  // namespace dexct

@@ -176,6 +176,9 @@ __global__ __launch_bounds__(256) void volume_ids_kernel(const uint8_t* __restri
   if (h[threadIdx.x]) atomicAdd(counts + threadIdx.x, (unsigned long long)h[threadIdx.x]);
 }
 
+// the grid cap of volume_ids_kernel (16 bytes per thread); tests/grid_caps.py holds its value, tests/test_gpu_grid_passes.py runs past it
+constexpr int kVolumeIdsMaxBlocks = 4096;
+
 struct Lut256 { uint8_t v[256]; };
 
 __global__ __launch_bounds__(256) void volume_remap_kernel(uint8_t* __restrict__ vol, size_t n, Lut256 lut) {
@@ -192,6 +195,9 @@ __global__ __launch_bounds__(256) void volume_remap_kernel(uint8_t* __restrict__
   if (blockIdx.x == 0)
     for (size_t i = n4 * 4 + threadIdx.x; i < n; i += 256) vol[i] = l[vol[i]];
 }
+
+// the grid cap of volume_remap_kernel (4 bytes per thread); tests/grid_caps.py holds its value, tests/test_gpu_grid_passes.py runs past it
+constexpr int kVolumeRemapMaxBlocks = 8192;
 
 }  // namespace dexct
 
@@ -366,7 +372,7 @@ int dexct_volume_ids(const uint8_t* vol, int64_t n_voxels, uint64_t* counts256, 
   hipStream_t st = as_stream(stream);
   DEXCT_HIP_TRY(hipMemsetAsync(counts256, 0, 256 * sizeof(uint64_t), st));
   size_t nblk = ((size_t)n_voxels / 16 + 255) / 256;
-  nblk = nblk < 1 ? 1 : (nblk > 4096 ? 4096 : nblk);
+  nblk = nblk < 1 ? 1 : (nblk > kVolumeIdsMaxBlocks ? kVolumeIdsMaxBlocks : nblk);
   hipLaunchKernelGGL(volume_ids_kernel, dim3((unsigned)nblk), dim3(256), 0, st, vol, (size_t)n_voxels,
                      reinterpret_cast<unsigned long long*>(counts256));
   DEXCT_LAUNCH_CHECK();
@@ -379,7 +385,7 @@ int dexct_volume_remap(uint8_t* vol, int64_t n_voxels, const uint8_t* lut256, vo
   Lut256 lut;
   for (int k = 0; k < 256; ++k) lut.v[k] = lut256[k];
   size_t nblk = ((size_t)n_voxels / 4 + 255) / 256;
-  nblk = nblk < 1 ? 1 : (nblk > 8192 ? 8192 : nblk);
+  nblk = nblk < 1 ? 1 : (nblk > kVolumeRemapMaxBlocks ? kVolumeRemapMaxBlocks : nblk);
   hipLaunchKernelGGL(volume_remap_kernel, dim3((unsigned)nblk), dim3(256), 0, as_stream(stream), vol, (size_t)n_voxels, lut);
   DEXCT_LAUNCH_CHECK();
   return DEXCT_OK;

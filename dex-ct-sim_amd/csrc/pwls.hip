@@ -233,9 +233,12 @@ __global__ __launch_bounds__(256) void pwls_update_kernel(const float* __restric
   if (penalty) block_add(acc, penalty);
 }
 
+// the grid cap of every kernel here; tests/grid_caps.py holds its value, tests/test_gpu_grid_passes.py runs past it
+constexpr int kPwlsMaxBlocks = 4096;
+
 static int64_t pwls_blocks(int64_t n) {
   int64_t nb = (n + 255) / 256;
-  return nb < 1 ? 1 : (nb > 4096 ? 4096 : nb);
+  return nb < 1 ? 1 : (nb > kPwlsMaxBlocks ? kPwlsMaxBlocks : nb);
 }
 
 constexpr int64_t kPwlsMaxElems = (int64_t)1 << 40;   // per plane: keeps every byte offset far inside int64

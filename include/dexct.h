@@ -747,7 +747,8 @@ int dexct_image_backproject(const dexct_fan_geom* geom, const dexct_ray_plan* pl
  *   dexct_sirt_residual: over lines k * line_step < n_lines of `line` values each (a line = one view: n_rows * n_channels),
  *                        r = (b - ax) / row_sum where row_sum > 0, else 0 (a ray that misses the grid); r may be NULL or
  *                        equal ax.  norm2 (may be NULL; not both NULL): one device float64, zeroed by the call, receives
- *                        sum (b - ax)^2 / row_sum over the same elements (float64 atomics across workgroups).
+ *                        sum (b - ax)^2 / row_sum over the same elements, formed in float64 from the float32 inputs
+ *                        (float64 atomics across workgroups).
  *   dexct_sirt_update:   x += relax * (g / col_sum) where col_sum > 0 (other pixels stay), then x = max(x, 0) if nonneg; n
  *                        values; relax > 0. */
 int dexct_sirt_residual(const float* b, const float* ax, const float* row_sum, int32_t n_lines, int32_t line_step,

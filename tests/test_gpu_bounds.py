@@ -405,11 +405,8 @@ OFFSETS = [0, 4, 8, 12]
 
 @pytest.fixture(scope='module')
 def bhc_table():
-    from dex_ct_sim_amd import bhc
-    E = np.linspace(10.0, 140.0, 131)
-    w = np.exp(-((E - 60.0) / 30.0) ** 2)
-    mu = 0.2 + 3.0 * (E / 20.0) ** -3
-    return bhc.build_table(w, mu, 'water')
+    import grid_caps
+    return grid_caps.bhc_table()                  # shared with tests/test_gpu_grid_passes.py
 
 
 @pytest.mark.parametrize('n', list(range(10)) + [4099, 100003])
