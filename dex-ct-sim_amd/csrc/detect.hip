@@ -3,7 +3,7 @@
 // of table rows, lengths in registers) that used to make siddon.hip 100 s of the library's 2-minute build.
 #include "common.h"
 #include "noise_sample.h"
-#include "siddon_detect.h"
+#include "proj_host.h"
 
 namespace dexct {
 
@@ -176,70 +176,23 @@ static int launch_detect(const ProjArgs& a, const Tables& t, hipStream_t st) {
   const size_t n_rays = (size_t)a.n_local_views * a.g.n_rows * a.g.n_channels;
   const bool wide = RMAX > 1 && a.layout == 1 && (a.g.n_rows % RMAX) == 0;
   const size_t n_thr = wide ? n_rays / RMAX : n_rays;
-  const size_t nblk = (n_thr + 255) / 256;
-  if (nblk > 0x7FFFFFFFull) return DEXCT_ERANGE;
-  if (wide) hipLaunchKernelGGL((detect_kernel<NMAT, RMAX>), dim3((unsigned)nblk), dim3(256), 0, st, a, t.mu, t.w, t.w2);
-  else hipLaunchKernelGGL((detect_kernel<NMAT, 1>), dim3((unsigned)nblk), dim3(256), 0, st, a, t.mu, t.w, t.w2);
+  dim3 grid;
+  if (!proj::grid_1d((n_thr + 255) / 256, grid)) return DEXCT_ERANGE;
+  if (wide) hipLaunchKernelGGL((detect_kernel<NMAT, RMAX>), grid, dim3(256), 0, st, a, t.mu, t.w, t.w2);
+  else hipLaunchKernelGGL((detect_kernel<NMAT, 1>), grid, dim3(256), 0, st, a, t.mu, t.w, t.w2);
   DEXCT_LAUNCH_CHECK();
   return DEXCT_OK;
 }
 
 int launch_detect_any(const ProjArgs& a, const Tables& t, hipStream_t st) {
-  switch (a.n_materials) {
-    case 2: return launch_detect<2>(a, t, st);
-    case 3: return launch_detect<3>(a, t, st);
-    case 4: return launch_detect<4>(a, t, st);
-    case 5: return launch_detect<5>(a, t, st);
-    case 6: return launch_detect<6>(a, t, st);
-    case 7: return launch_detect<7>(a, t, st);
-    case 8: return launch_detect<8>(a, t, st);
-    case 9: return launch_detect<9>(a, t, st);
-    case 10: return launch_detect<10>(a, t, st);
-    case 11: return launch_detect<11>(a, t, st);
-    case 12: return launch_detect<12>(a, t, st);
-    case 13: return launch_detect<13>(a, t, st);
-    case 14: return launch_detect<14>(a, t, st);
-    case 15: return launch_detect<15>(a, t, st);
-    case 16: return launch_detect<16>(a, t, st);
-    case 17: return launch_detect<17>(a, t, st);
-    case 18: return launch_detect<18>(a, t, st);
-    case 19: return launch_detect<19>(a, t, st);
-    case 20: return launch_detect<20>(a, t, st);
-    case 21: return launch_detect<21>(a, t, st);
-    case 22: return launch_detect<22>(a, t, st);
-    case 23: return launch_detect<23>(a, t, st);
-    case 24: return launch_detect<24>(a, t, st);
-    case 25: return launch_detect<25>(a, t, st);
-    case 26: return launch_detect<26>(a, t, st);
-    case 27: return launch_detect<27>(a, t, st);
-    case 28: return launch_detect<28>(a, t, st);
-    case 29: return launch_detect<29>(a, t, st);
-    case 30: return launch_detect<30>(a, t, st);
-    case 31: return launch_detect<31>(a, t, st);
-    case 32: return launch_detect<32>(a, t, st);
-    case 33: return launch_detect<33>(a, t, st);
-    case 34: return launch_detect<34>(a, t, st);
-    case 35: return launch_detect<35>(a, t, st);
-    case 36: return launch_detect<36>(a, t, st);
-    case 37: return launch_detect<37>(a, t, st);
-    case 38: return launch_detect<38>(a, t, st);
-    case 39: return launch_detect<39>(a, t, st);
-    case 40: return launch_detect<40>(a, t, st);
-    case 41: return launch_detect<41>(a, t, st);
-    case 42: return launch_detect<42>(a, t, st);
-    case 43: return launch_detect<43>(a, t, st);
-    case 44: return launch_detect<44>(a, t, st);
-    case 45: return launch_detect<45>(a, t, st);
-    case 46: return launch_detect<46>(a, t, st);
-    case 47: return launch_detect<47>(a, t, st);
-    case 48: return launch_detect<48>(a, t, st);
-    default: break;
-  }
+  if (a.n_materials >= 2 && a.n_materials <= kManyMaterials)      // lengths in registers: one instantiation per count
+    return proj::for_materials_from<2>(a.n_materials, std::make_integer_sequence<int, kManyMaterials - 1>{},
+                                       [&](auto nm) { return launch_detect<decltype(nm)::value>(a, t, st); });
   // 49..256 table rows: the general detection (exponents of 32 energies in registers, run-time material loop)
   const size_t n_rays = (size_t)a.n_local_views * a.g.n_rows * a.g.n_channels;
-  const size_t nblk = (n_rays + 255) / 256;
-  if (nblk > 0x7FFFFFFFull) return DEXCT_ERANGE;
-  hipLaunchKernelGGL(detect_kernel_chunked, dim3((unsigned)nblk), dim3(256), 0, st, a, t.mu, t.w, t.w2);
+  dim3 grid;
+  if (!proj::grid_1d((n_rays + 255) / 256, grid)) return DEXCT_ERANGE;
+  hipLaunchKernelGGL(detect_kernel_chunked, grid, dim3(256), 0, st, a, t.mu, t.w, t.w2);
   DEXCT_LAUNCH_CHECK();
   return DEXCT_OK;
 }

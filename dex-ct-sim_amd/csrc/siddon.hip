@@ -31,10 +31,8 @@
 //                 workgroup prefix sum (legal because counts are order independent and corrections
 //                 only arise in crossing slabs, whose relative order is kept).  <= 4 materials.
 // Tables are wave-uniform and are read through the scalar cache (s_load), not LDS.
-#include <cstdlib>
-
 #include "common.h"
-#include "siddon_detect.h"
+#include "proj_host.h"
 
 namespace dexct {
 
@@ -372,8 +370,7 @@ struct SlabRec {
 //  * tile: logical ids walk groups of kViewTile consecutive views with the view index fastest, then the
 //    channel.  The ~400 workgroups an XCD runs at once are then (kViewTile views x ~50 channels): rays of
 //    neighbouring views through the same voxel columns are in flight together and hit in L2 instead of
-//    going to the Infinity Cache / HBM once per view.
-constexpr int kViewTileDefault = 8;
+//    going to the Infinity Cache / HBM once per view.  (kViewTile: proj::knob::kViewTile, 8 views)
 
 struct BlockRay { int v, c, chunk; };
 
@@ -1042,10 +1039,8 @@ static int launch_rays(const ProjArgs& a, const Tables& t, hipStream_t st) {
   size_t lds = NM > 0 ? 0 : (size_t)2 * a.n_materials * B * sizeof(float);
   if constexpr (NM > 0) {
     // register accumulators: one wave per workgroup (no lanes idle beyond the last partial wave of a view: 800 channels
-    // are 12.5 waves, not 4 x 256 threads) and batches of slabs with all their loads in flight (DEXCT_RAYS_BATCH=1/4/8/16;
-    // measured on the reference's 1000 x 800 single-row scan: 0.620 / 0.440 / 0.450 / 0.457 ms, profiles/r03_kernels.md)
-    int batch = 4;
-    if (const char* e = getenv("DEXCT_RAYS_BATCH")) batch = atoi(e);
+    // are 12.5 waves, not 4 x 256 threads) and batches of slabs with all their loads in flight
+    const int batch = proj::read_knob(proj::knob::kRaysBatch);
     dim3 grid1((a.g.n_channels + 63) / 64, a.g.n_rows, a.n_local_views);
     if (batch == 8) hipLaunchKernelGGL((rays_kernel<NM, 64, 8>), grid1, dim3(64), 0, st, a, t.mu, t.w, t.w2);
     else if (batch == 4) hipLaunchKernelGGL((rays_kernel<NM, 64, 4>), grid1, dim3(64), 0, st, a, t.mu, t.w, t.w2);
@@ -1072,21 +1067,20 @@ template <int NM>
 static int launch_rows(const ProjArgs& a, const Tables& t, hipStream_t st) {
   constexpr int B = NM > 0 ? kBlock : kLdsBlock;
   const int n_chunks = (a.g.n_rows + B - 1) / B;
-  const size_t nblk = (size_t)a.n_local_views * a.g.n_channels * n_chunks;
-  if (nblk > 0x7FFFFFFFull) return DEXCT_ERANGE;
+  dim3 grid;
+  if (!proj::grid_1d((size_t)a.n_local_views * a.g.n_channels * n_chunks, grid)) return DEXCT_ERANGE;
   size_t lds = NM > 0 ? 0 : (size_t)2 * a.n_materials * B * sizeof(float);
   if (NM == 0 && a.n_materials > kManyMaterials) {      // 49..256 materials: LDS columns of 64 lanes
     constexpr int B2 = 64;
     const int n_chunks2 = (a.g.n_rows + B2 - 1) / B2;
-    const size_t nblk2 = (size_t)a.n_local_views * a.g.n_channels * n_chunks2;
-    if (nblk2 > 0x7FFFFFFFull) return DEXCT_ERANGE;
+    if (!proj::grid_1d((size_t)a.n_local_views * a.g.n_channels * n_chunks2, grid)) return DEXCT_ERANGE;
     lds = (size_t)2 * a.n_materials * B2 * sizeof(float);
     DEXCT_ALLOW_LDS((rows_kernel<NM, B2>), lds);
-    hipLaunchKernelGGL((rows_kernel<NM, B2>), dim3((unsigned)nblk2), dim3(B2), lds, st, a, t.mu, t.w, t.w2, n_chunks2);
+    hipLaunchKernelGGL((rows_kernel<NM, B2>), grid, dim3(B2), lds, st, a, t.mu, t.w, t.w2, n_chunks2);
     DEXCT_LAUNCH_CHECK();
     return DEXCT_OK;
   }
-  hipLaunchKernelGGL((rows_kernel<NM, B>), dim3((unsigned)nblk), dim3(B), lds, st, a, t.mu, t.w, t.w2, n_chunks);
+  hipLaunchKernelGGL((rows_kernel<NM, B>), grid, dim3(B), lds, st, a, t.mu, t.w, t.w2, n_chunks);
   DEXCT_LAUNCH_CHECK();
   return DEXCT_OK;
 }
@@ -1095,12 +1089,12 @@ template <int NM, int B>
 static int launch_rows4_b(const ProjArgs& a, const Tables& t, hipStream_t st) {
   const int rows_per_block = 4 * B;
   const int n_chunks = (a.g.n_rows + rows_per_block - 1) / rows_per_block;
-  const size_t nblk = (size_t)a.n_local_views * a.g.n_channels * n_chunks;
-  if (nblk > 0x7FFFFFFFull) return DEXCT_ERANGE;
+  dim3 grid;
+  if (!proj::grid_1d((size_t)a.n_local_views * a.g.n_channels * n_chunks, grid)) return DEXCT_ERANGE;
   if (a.acc_out)
-    hipLaunchKernelGGL((rows4_kernel<NM, B, true>), dim3((unsigned)nblk), dim3(B), 0, st, a, t.mu, t.w, t.w2, n_chunks);
+    hipLaunchKernelGGL((rows4_kernel<NM, B, true>), grid, dim3(B), 0, st, a, t.mu, t.w, t.w2, n_chunks);
   else
-    hipLaunchKernelGGL((rows4_kernel<NM, B, false>), dim3((unsigned)nblk), dim3(B), 0, st, a, t.mu, t.w, t.w2, n_chunks);
+    hipLaunchKernelGGL((rows4_kernel<NM, B, false>), grid, dim3(B), 0, st, a, t.mu, t.w, t.w2, n_chunks);
   DEXCT_LAUNCH_CHECK();
   return DEXCT_OK;
 }
@@ -1117,21 +1111,17 @@ static int launch_rows4(const ProjArgs& a, const Tables& t, hipStream_t st) {
 // Tile shape of rows4t_kernel: 8 pairs = 2 views x 4 channels, barrier every 64 slabs - the fastest tile of the sweep of
 // round 2 (profiles/r02_tiled_1024.md: 21.8 ms on the 1024^3 share; 16 : 4 : 16 has the lowest fabric traffic, 61-66 GB, but
 // takes 40.6 ms).  The kernel is opt-in (kernel = 5, A/B against the row kernels; rows16_kernel on the packed volume superseded
-// both); the other tile shapes and the 16-row fetch form of the sweep left the library in round 5 (they were 100 s of its
-// 2-minute build).
+// both) and only dexct_siddon_project launches it, so its material-group form (GROUPED) is not instantiated; the other tile
+// shapes and the 16-row fetch form of the sweep left the library in round 5 (they were 100 s of its 2-minute build).
 template <int NM>
 static int launch_rows4t(const ProjArgs& a, const Tables& t, hipStream_t st) {
   constexpr int kPairs = 8, kSub = 64;
   const int tile_v = 2, tile_c = kPairs / tile_v;
   const int n_z = (a.g.n_rows + 255) / 256;
-  const size_t nblk = (size_t)((a.n_local_views + tile_v - 1) / tile_v) * ((a.g.n_channels + tile_c - 1) / tile_c) * n_z;
-  if (nblk > 0x7FFFFFFFull) return DEXCT_ERANGE;
-  if (a.acc_out)
-    hipLaunchKernelGGL((rows4t_kernel<NM, kPairs, kSub, true>), dim3((unsigned)nblk), dim3(kPairs * 64), 0, st, a, t.mu, t.w, t.w2,
-                       tile_v, n_z);
-  else
-    hipLaunchKernelGGL((rows4t_kernel<NM, kPairs, kSub, false>), dim3((unsigned)nblk), dim3(kPairs * 64), 0, st, a, t.mu, t.w, t.w2,
-                       tile_v, n_z);
+  dim3 grid;
+  if (!proj::grid_1d((size_t)((a.n_local_views + tile_v - 1) / tile_v) * ((a.g.n_channels + tile_c - 1) / tile_c) * n_z, grid))
+    return DEXCT_ERANGE;
+  hipLaunchKernelGGL((rows4t_kernel<NM, kPairs, kSub, false>), grid, dim3(kPairs * 64), 0, st, a, t.mu, t.w, t.w2, tile_v, n_z);
   DEXCT_LAUNCH_CHECK();
   return DEXCT_OK;
 }
@@ -1148,90 +1138,48 @@ int dexct_siddon_project(const dexct_fan_geom* geom, const dexct_ray_plan* plan,
                          float* pathlen, int32_t kernel, int32_t layout, const float* weights2, float* variance,
                          const dexct_log_out* log_out, void* stream) {
   if (!geom || !plan || !mu || !weights || !counts) return DEXCT_EINVAL;
-  if (view_begin < 0 || view_end > geom->n_views || view_end <= view_begin) return DEXCT_EINVAL;
+  if (!proj::views_ok(*geom, view_begin, view_end)) return DEXCT_EINVAL;
   if (n_materials < 1 || n_energies < 1 || n_spectra < 1 || geom->n_rows < 1) return DEXCT_EINVAL;
   if (n_materials > DEXCT_MAX_MATERIALS || n_spectra > DEXCT_MAX_SPECTRA) return DEXCT_ERANGE;
-  if (geom->z_first < 0 || geom->z_first + geom->n_rows > geom->nz) return DEXCT_EINVAL;
-  if ((uint64_t)geom->nx * geom->ny * geom->nz > 0xFFFFFFFEull) return DEXCT_ERANGE;  // 32-bit voxel offsets
-  const bool can4 = vol_zf && n_materials >= 2 && n_materials <= 4 && geom->nz % 4 == 0 && geom->z_first % 4 == 0;
+  if (!proj::stack_ok(*geom)) return DEXCT_EINVAL;
+  if (!proj::offsets_fit(*geom)) return DEXCT_ERANGE;
+  const bool can4 = vol_zf && n_materials >= 2 && n_materials <= 4 && proj::stack_aligned(*geom, 4);
   if (kernel == 0) kernel = (vol_zf && geom->n_rows >= 64) ? (can4 ? 3 : 2) : 1;
   if (kernel == 1 && (!vol_yx || !vol_xy)) return DEXCT_EINVAL;
   if (kernel == 2 && !vol_zf) return DEXCT_EINVAL;
   if ((kernel == 3 || kernel == 5) && !can4) return DEXCT_EINVAL;
   if (kernel < 1 || kernel > 6 || kernel == 4) return DEXCT_EINVAL;
   if (kernel == 6 && (!vol_yx || !vol_xy || n_materials > 4 || variance)) return DEXCT_EINVAL;
-  if (layout != 0 && layout != 1) return DEXCT_EINVAL;
-  if ((variance != nullptr) != (weights2 != nullptr)) return DEXCT_EINVAL;
-  if (geom->n_rows > 65535 || view_end - view_begin > 65535) return DEXCT_ERANGE;
-  ProjArgs a;
-  a.g = *geom;
-  a.plan = plan;
+  if (!proj::layout_ok(layout)) return DEXCT_EINVAL;
+  // (no dexct_noise here: the variance goes to dexct_add_noise)
+  const proj::NoiseLog nl = proj::noise_log_args(weights2, variance, nullptr, log_out, n_spectra, n_materials, proj::NoiseBy::kOwnLoop);
+  if (nl.noise_rc != DEXCT_OK) return nl.noise_rc;
+  if (!proj::fits_16bit(*geom, view_begin, view_end)) return DEXCT_ERANGE;
+  if (nl.log_rc != DEXCT_OK) return nl.log_rc;
+  ProjArgs a = proj::fill_proj_args(*geom, plan, view_begin, view_end, n_materials, n_energies, n_spectra, counts, pathlen, variance,
+                                    layout, nl);
   a.vol_yx = vol_yx;
   a.vol_xy = vol_xy;
   a.vol_zf = vol_zf;
-  a.n_local_views = view_end - view_begin;
-  a.n_materials = n_materials;
-  a.n_energies = n_energies;
-  a.n_spectra = n_spectra;
-  a.counts = counts;
-  a.pathlen = pathlen;
-  a.variance = variance;
-  a.acc_out = nullptr;
-  a.mat_base = 0;
-  a.layout = layout;
-  if (set_log_out(a, log_out, variance) != DEXCT_OK) return DEXCT_EINVAL;
+  a.view_tile = proj::read_knob(proj::knob::kViewTile);
   const Tables t{mu, weights, weights2};
-  a.view_tile = kViewTileDefault;
-  if (const char* e = getenv("DEXCT_VIEW_TILE")) { const int t = atoi(e); if (t >= 1 && t <= 4096) a.view_tile = t; }   // tuning knob
   hipStream_t st = as_stream(stream);
-  if (kernel == 1) {
-    switch (n_materials) {
-      case 1: return launch_rays<1>(a, t, st);
-      case 2: return launch_rays<2>(a, t, st);
-      case 3: return launch_rays<3>(a, t, st);
-      case 4: return launch_rays<4>(a, t, st);
-      default: return launch_rays<0>(a, t, st);
-    }
-  }
-  if (kernel == 2) {
-    switch (n_materials) {
-      case 1: return launch_rows<1>(a, t, st);
-      case 2: return launch_rows<2>(a, t, st);
-      case 3: return launch_rows<3>(a, t, st);
-      case 4: return launch_rows<4>(a, t, st);
-      default: return launch_rows<0>(a, t, st);
-    }
-  }
-  if (kernel == 6) {        // one wavefront per ray (the north-star mapping; A/B and single-row scans)
-    switch (n_materials) {
-      case 1: return launch_wave_ray<1>(a, t, st);
-      case 2: return launch_wave_ray<2>(a, t, st);
-      case 3: return launch_wave_ray<3>(a, t, st);
-      default: return launch_wave_ray<4>(a, t, st);
-    }
-  }
-  if (kernel == 5) {        // tiled lockstep form: several (view, channel) pairs per workgroup, 256 rows per wave
-    switch (n_materials) {
-      case 2: return launch_rows4t<2>(a, t, st);
-      case 3: return launch_rows4t<3>(a, t, st);
-      default: return launch_rows4t<4>(a, t, st);
-    }
-  }
-  switch (n_materials) {
-    case 2: return launch_rows4<2>(a, t, st);
-    case 3: return launch_rows4<3>(a, t, st);
-    default: return launch_rows4<4>(a, t, st);
-  }
+  if (kernel == 1) return proj::for_materials<1, 2, 3, 4, 0>(n_materials, [&](auto nm) { return launch_rays<decltype(nm)::value>(a, t, st); });
+  if (kernel == 2) return proj::for_materials<1, 2, 3, 4, 0>(n_materials, [&](auto nm) { return launch_rows<decltype(nm)::value>(a, t, st); });
+  if (kernel == 6)          // one wavefront per ray (the north-star mapping; A/B and single-row scans)
+    return proj::for_materials<1, 2, 3, 4>(n_materials, [&](auto nm) { return launch_wave_ray<decltype(nm)::value>(a, t, st); });
+  if (kernel == 5)          // tiled lockstep form: several (view, channel) pairs per workgroup, 256 rows per wave
+    return proj::for_materials<2, 3, 4>(n_materials, [&](auto nm) { return launch_rows4t<decltype(nm)::value>(a, t, st); });
+  return proj::for_materials<2, 3, 4>(n_materials, [&](auto nm) { return launch_rows4<decltype(nm)::value>(a, t, st); });
 }
 
 int dexct_volume_groups(const uint8_t* vol_zf, int64_t n_voxels, int32_t n_materials, uint8_t* codes, void* stream) {
   if (!vol_zf || !codes || n_voxels <= 0 || n_materials < 2) return DEXCT_EINVAL;
   if (n_materials > kMaxGrouped) return DEXCT_ERANGE;
-  const int n_groups = (n_materials - 1 + 2) / 3;
-  const size_t nblk = ((size_t)n_voxels / 4 + 256) / 256;
-  if (nblk > 0x7FFFFFFFull) return DEXCT_ERANGE;
-  hipLaunchKernelGGL(group_codes_kernel, dim3((unsigned)nblk), dim3(256), 0, as_stream(stream), vol_zf, (size_t)n_voxels,
-                     n_groups, codes);
+  dim3 grid;
+  if (!proj::grid_1d(((size_t)n_voxels / 4 + 256) / 256, grid)) return DEXCT_ERANGE;
+  hipLaunchKernelGGL(group_codes_kernel, grid, dim3(256), 0, as_stream(stream), vol_zf, (size_t)n_voxels,
+                     proj::n_groups(n_materials, true), codes);
   DEXCT_LAUNCH_CHECK();
   return DEXCT_OK;
 }
@@ -1242,45 +1190,30 @@ int dexct_siddon_project_grouped(const dexct_fan_geom* geom, const dexct_ray_pla
                                  float* acc_scratch, int32_t layout, const float* weights2, float* variance,
                                  const dexct_log_out* log_out, const dexct_noise* noise, void* stream) {
   if (!geom || !plan || !codes || !mu || !weights || !counts || !acc_scratch) return DEXCT_EINVAL;
-  if (view_begin < 0 || view_end > geom->n_views || view_end <= view_begin) return DEXCT_EINVAL;
+  if (!proj::views_ok(*geom, view_begin, view_end)) return DEXCT_EINVAL;
   if (n_materials < 2 || n_energies < 1 || n_spectra < 1 || geom->n_rows < 1) return DEXCT_EINVAL;
   if (n_materials > kMaxGrouped || n_spectra > DEXCT_MAX_SPECTRA) return DEXCT_ERANGE;
-  if (geom->z_first < 0 || geom->z_first + geom->n_rows > geom->nz) return DEXCT_EINVAL;
-  if (geom->nz % 4 != 0 || geom->z_first % 4 != 0) return DEXCT_EINVAL;
-  if ((uint64_t)geom->nx * geom->ny * geom->nz > 0xFFFFFFFEull) return DEXCT_ERANGE;
-  if (layout != 0 && layout != 1) return DEXCT_EINVAL;
-  if (geom->n_rows > 65535 || view_end - view_begin > 65535) return DEXCT_ERANGE;
-  ProjArgs a;
-  a.g = *geom;
-  a.plan = plan;
-  a.vol_yx = nullptr;
-  a.vol_xy = nullptr;
-  a.n_local_views = view_end - view_begin;
-  a.n_materials = n_materials;
-  a.n_energies = n_energies;
-  a.n_spectra = n_spectra;
-  a.counts = counts;
-  a.pathlen = pathlen;
-  a.variance = variance;
-  a.layout = layout;
+  if (!proj::stack_ok(*geom)) return DEXCT_EINVAL;
+  if (!proj::stack_aligned(*geom, 4)) return DEXCT_EINVAL;
+  if (!proj::offsets_fit(*geom)) return DEXCT_ERANGE;
+  if (!proj::layout_ok(layout)) return DEXCT_EINVAL;
+  if (!proj::fits_16bit(*geom, view_begin, view_end)) return DEXCT_ERANGE;
+  const proj::NoiseLog nl = proj::noise_log_args(weights2, variance, noise, log_out, n_spectra, n_materials, proj::NoiseBy::kGroupPass);
+  if (nl.status() != DEXCT_OK) return nl.status();
+  ProjArgs a = proj::fill_proj_args(*geom, plan, view_begin, view_end, n_materials, n_energies, n_spectra, counts, pathlen, variance,
+                                    layout, nl);
+  proj::copy_noise(a, view_begin, nl);
   a.acc_out = acc_scratch;
-  { const int nrc = set_noise(a, view_begin, weights2, variance, noise); if (nrc != DEXCT_OK) return nrc; }
-  // (the log of a noisy sinogram is the log of the SAMPLED counts: written here only when the detection pass draws the sample)
-  if (set_log_out(a, log_out, a.sample ? nullptr : variance) != DEXCT_OK) return DEXCT_EINVAL;
-  a.view_tile = kViewTileDefault;
-  if (const char* e = getenv("DEXCT_VIEW_TILE")) { const int t = atoi(e); if (t >= 1 && t <= 4096) a.view_tile = t; }
+  a.view_tile = proj::read_knob(proj::knob::kViewTile);
   const Tables t{mu, weights, weights2};
   hipStream_t st = as_stream(stream);
   const size_t n_vox = (size_t)geom->nx * geom->ny * geom->nz;
-  const int n_groups = (n_materials - 1 + 2) / 3;
-  for (int g = 0; g < n_groups; ++g) {
+  for (int g = 0; g < proj::n_groups(n_materials, true); ++g) {
     a.vol_zf = codes + (size_t)g * n_vox;
     a.mat_base = 3 * g;
-    const int left = n_materials - 1 - 3 * g;           // materials in this group: 1..3
-    int rc;
-    if (left >= 3) rc = launch_rows4<4>(a, t, st);
-    else if (left == 2) rc = launch_rows4<3>(a, t, st);
-    else rc = launch_rows4<2>(a, t, st);
+    // (codes 0..3 of a group: its materials and "none of them")
+    const int rc = proj::for_materials<4, 3, 2>(proj::group_size(n_materials, true, g) + 1,
+                                                [&](auto nm) { return launch_rows4<decltype(nm)::value>(a, t, st); });
     if (rc != DEXCT_OK) return rc;
   }
   return launch_detect_any(a, t, st);

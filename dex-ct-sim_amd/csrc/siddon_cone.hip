@@ -20,7 +20,7 @@
 
 #include "common.h"
 #include "noise_sample.h"
-#include "siddon_detect.h"
+#include "proj_host.h"
 
 namespace dexct {
 
@@ -261,19 +261,19 @@ __global__ __launch_bounds__(CB) void cone_kernel(ConeArgs a, const float* __res
 }
 
 template <int NM>
-static int launch_cone(const ConeArgs& a, const float* mu, const float* w, const float* w2, hipStream_t st) {
+static int launch_cone(const ConeArgs& a, const Tables& t, hipStream_t st) {
   if (NM == 0 && a.n_materials > kManyMaterials) {       // 49..256 materials: LDS columns of 64 lanes (<= 128 KB)
     constexpr int B2 = 64;
     const size_t lds2 = (size_t)2 * a.n_materials * B2 * sizeof(float);
     DEXCT_ALLOW_LDS((cone_kernel<NM, B2>), lds2);
     dim3 grid2((a.g.n_channels + B2 - 1) / B2, a.g.n_rows, a.n_local_views);
-    hipLaunchKernelGGL((cone_kernel<NM, B2>), grid2, dim3(B2), lds2, st, a, mu, w, w2);
+    hipLaunchKernelGGL((cone_kernel<NM, B2>), grid2, dim3(B2), lds2, st, a, t.mu, t.w, t.w2);
     DEXCT_LAUNCH_CHECK();
     return DEXCT_OK;
   }
   dim3 grid((a.g.n_channels + kConeBlock - 1) / kConeBlock, a.g.n_rows, a.n_local_views);
   const size_t lds = NM > 0 ? 0 : (size_t)2 * a.n_materials * kConeBlock * sizeof(float);
-  hipLaunchKernelGGL((cone_kernel<NM, kConeBlock>), grid, dim3(kConeBlock), lds, st, a, mu, w, w2);
+  hipLaunchKernelGGL((cone_kernel<NM, kConeBlock>), grid, dim3(kConeBlock), lds, st, a, t.mu, t.w, t.w2);
   DEXCT_LAUNCH_CHECK();
   return DEXCT_OK;
 }
@@ -789,24 +789,6 @@ __global__ __launch_bounds__(256) void cone_layout_kernel(const uint8_t* __restr
   out[i] = val;
 }
 
-// the noise arguments of the cone entry points (struct dexct_noise): weights2 switches the variance on and needs somewhere for
-// it to go; the log of a noisy sinogram is the log of the SAMPLED counts, so log_out needs the sample
-static int cone_noise_args(const float* weights2, const float* variance, const dexct_noise* noise, const dexct_log_out* log_out) {
-  const bool sample = noise && noise->sample;
-  if (!weights2) return (variance || sample) ? DEXCT_EINVAL : DEXCT_OK;
-  if (!variance && !sample) return DEXCT_EINVAL;
-  if (!sample && log_out && log_out->sino_log) return DEXCT_EINVAL;
-  return DEXCT_OK;
-}
-
-static void set_cone_noise(ConeArgs& a, float* variance, const dexct_noise* noise) {
-  const bool sample = noise && noise->sample;
-  a.variance = variance;
-  a.sample = sample ? 1 : 0;
-  a.seed_lo = sample ? (uint32_t)noise->seed : 0u;
-  a.seed_hi = sample ? (uint32_t)(noise->seed >> 32) : 0u;
-}
-
 // the guarded layout once per group of three materials: layout g holds 8 * (id - 3 g) for ids 3g .. 3g + 2 and 24 ("outside":
 // a voxel that belongs to nobody) for every other id - the row kernels then accumulate exactly the sums of these three
 // materials (the per-material sums of orc_cone_pathlen are independent of each other)
@@ -826,6 +808,30 @@ __global__ __launch_bounds__(256) void cone_layout_groups_kernel(const uint8_t* 
   }
 }
 
+// What every ConeArgs holds; the rest is value-initialised (the entry points set the volumes, acc_out and mat_base).
+static ConeArgs fill_cone_args(const dexct_fan_geom& g, const dexct_ray_plan* plan, const double* view_cs, const double* chan_cs,
+                               const double* row_z, double src_z, int32_t view_begin, int32_t view_end, int32_t n_materials,
+                               int32_t n_energies, int32_t n_spectra, float* counts, float* pathlen, float* variance,
+                               const proj::NoiseLog& nl) {
+  ConeArgs a{};
+  a.g = g;
+  a.plan = plan;
+  a.view_cs = view_cs;
+  a.chan_cs = chan_cs;
+  a.row_z = row_z;
+  a.src_z = src_z;
+  a.n_local_views = view_end - view_begin;
+  a.n_materials = n_materials;
+  a.n_energies = n_energies;
+  a.n_spectra = n_spectra;
+  a.counts = counts;
+  a.pathlen = pathlen;
+  a.variance = variance;
+  proj::copy_log(a, nl);
+  proj::copy_noise(a, view_begin, nl);
+  return a;
+}
+
 }  // namespace dexct
 
 using namespace dexct;
@@ -838,46 +844,22 @@ extern "C" int dexct_cone_project(const dexct_fan_geom* geom, const dexct_ray_pl
                                   const float* weights2, float* variance, const dexct_noise* noise, void* stream) {
   if (!geom || !plan || !view_cs || !chan_cs || !row_z || !vol_yx || !vol_xy || !mu || !weights || !counts)
     return DEXCT_EINVAL;
-  if (cone_noise_args(weights2, variance, noise, log_out) != DEXCT_OK) return DEXCT_EINVAL;
-  if (view_begin < 0 || view_end > geom->n_views || view_end <= view_begin) return DEXCT_EINVAL;
+  const proj::NoiseLog nl = proj::noise_log_args(weights2, variance, noise, log_out, n_spectra, n_materials, proj::NoiseBy::kOwnLoop);
+  if (nl.status() != DEXCT_OK) return nl.status();
+  if (!proj::views_ok(*geom, view_begin, view_end)) return DEXCT_EINVAL;
   if (n_materials < 1 || n_energies < 1 || n_spectra < 1 || geom->n_rows < 1) return DEXCT_EINVAL;
   if (n_materials > DEXCT_MAX_MATERIALS || n_spectra > DEXCT_MAX_SPECTRA) return DEXCT_ERANGE;
-  if ((uint64_t)geom->nx * geom->ny * geom->nz > 0xFFFFFFFEull) return DEXCT_ERANGE;
-  if (geom->n_rows > 65535 || view_end - view_begin > 65535) return DEXCT_ERANGE;
-  // at most one z-plane per dominant-axis slab: |dz/du| <= 1 for every ray.  du/ds >= 1/(sqrt(2) max(dx, dy))
-  // along the dominant axis, dz/ds <= max|z_det - z_src| / SDD (max_abs_dz is supplied by the caller, who
-  // owns row_z on the device).
-  const double dmax = geom->dx > geom->dy ? geom->dx : geom->dy;
-  if (!(max_abs_dz >= 0) || max_abs_dz / geom->sdd / geom->dz * dmax * 1.4142135623730951 > 1.0) return DEXCT_ERANGE;
-  ConeArgs a;
-  a.g = *geom;
-  a.plan = plan;
-  a.view_cs = view_cs;
-  a.chan_cs = chan_cs;
-  a.row_z = row_z;
-  a.src_z = src_z;
+  if (!proj::offsets_fit(*geom)) return DEXCT_ERANGE;
+  if (!proj::fits_16bit(*geom, view_begin, view_end)) return DEXCT_ERANGE;
+  if (!proj::cone_slope_ok(*geom, max_abs_dz)) return DEXCT_ERANGE;
+  ConeArgs a = fill_cone_args(*geom, plan, view_cs, chan_cs, row_z, src_z, view_begin, view_end, n_materials, n_energies, n_spectra,
+                              counts, pathlen, variance, nl);
   a.vol_yx = vol_yx;
   a.vol_xy = vol_xy;
-  a.view_begin = view_begin;
-  a.n_local_views = view_end - view_begin;
-  a.n_materials = n_materials;
-  a.n_energies = n_energies;
-  a.n_spectra = n_spectra;
-  a.counts = counts;
-  a.pathlen = pathlen;
-  a.sino_log = log_out ? log_out->sino_log : nullptr;
-  for (int s = 0; s < DEXCT_MAX_SPECTRA; ++s) a.air[s] = log_out ? log_out->air[s] : 1.0f;
-  set_cone_noise(a, variance, noise);
+  const Tables t{mu, weights, weights2};
   hipStream_t st = as_stream(stream);
-  switch (n_materials) {
-    case 1: return launch_cone<1>(a, mu, weights, weights2, st);
-    case 2: return launch_cone<2>(a, mu, weights, weights2, st);
-    case 3: return launch_cone<3>(a, mu, weights, weights2, st);
-    case 4: return launch_cone<4>(a, mu, weights, weights2, st);
-    default: return launch_cone<0>(a, mu, weights, weights2, st);
-  }
+  return proj::for_materials<1, 2, 3, 4, 0>(n_materials, [&](auto nm) { return launch_cone<decltype(nm)::value>(a, t, st); });
 }
-
 
 extern "C" int64_t dexct_cone_layout_bytes(int32_t nx, int32_t ny, int32_t nz) {
   if (nx <= 0 || ny <= 0 || nz <= 0) return 0;
@@ -894,106 +876,59 @@ extern "C" int dexct_cone_layout(const uint8_t* vol, int32_t nx, int32_t ny, int
   return DEXCT_OK;
 }
 
-// what both row-kernel entry points check
+namespace dexct {
+
+// what both row-kernel entry points check, in this order
 static int cone_rows_checks(const dexct_fan_geom* geom, int32_t view_begin, int32_t view_end, int32_t n_energies, int32_t n_spectra,
                             double max_abs_dz) {
-  if (view_begin < 0 || view_end > geom->n_views || view_end <= view_begin) return DEXCT_EINVAL;
+  if (!proj::views_ok(*geom, view_begin, view_end)) return DEXCT_EINVAL;
   if (n_energies < 1 || n_spectra < 1 || geom->n_rows < 1) return DEXCT_EINVAL;
   if (n_spectra > DEXCT_MAX_SPECTRA) return DEXCT_ERANGE;
   if (dexct_cone_layout_bytes(geom->nx, geom->ny, geom->nz) > 0xFFFFFFFEll) return DEXCT_ERANGE;
-  if (geom->n_rows > 65535 || view_end - view_begin > 65535) return DEXCT_ERANGE;
-  const double dmax = geom->dx > geom->dy ? geom->dx : geom->dy;
-  if (!(max_abs_dz >= 0) || max_abs_dz / geom->sdd / geom->dz * dmax * 1.4142135623730951 > 1.0) return DEXCT_ERANGE;
+  if (!proj::fits_16bit(*geom, view_begin, view_end)) return DEXCT_ERANGE;
+  if (!proj::cone_slope_ok(*geom, max_abs_dz)) return DEXCT_ERANGE;
   return DEXCT_OK;
 }
 
 // one launch of the row kernels on the layout vol_zc; nm = the materials (codes) the layout holds: 1..3
-static int launch_cone_rows(const ConeArgs& a, const uint8_t* vol_zc, int nm, const float* mu, const float* weights,
-                            const float* weights2, hipStream_t st) {
-  const dexct_fan_geom* geom = &a.g;
-  const int n_chunks = (geom->n_rows + kConeRows - 1) / kConeRows;
-  const size_t nblk = (size_t)a.n_local_views * geom->n_channels * n_chunks;
-  if (nblk > 0x7FFFFFFFull) return DEXCT_ERANGE;
-  // views per tile of the block order: 1 = all channels of a view before the next view (round 3: 9.6 -> 9.2 ms on a
-  // 100-view scan, whose views 3.6 degrees apart share no columns; no difference at 0.36 degrees)
-  int view_tile = 1;
-  if (const char* te = getenv("DEXCT_CONE_VIEW_TILE")) view_tile = atoi(te) > 0 ? atoi(te) : 1;      // tuning knob
-  // round 3: columns staged in LDS (cone_cols_kernel) whenever a column fits the reserved bytes; DEXCT_CONE_COLS=0 = A/B
-  const char* ce = getenv("DEXCT_CONE_COLS");
-  const uint32_t zs = cone_zs(geom->nz);
-  if (!(ce && atoi(ce) == 0) && zs <= 1056u) {
-    // slabs per staged batch: 4 (default: 64 VGPRs and 17 KB of LDS = 8 waves per SIMD; 9.6 ms) or 8 (92 VGPRs, 26 KB:
-    // 5 waves; 10.4 ms) - the loop waits for the staged loads of the next batch, so waves in flight are what counts
-    const char* ke = getenv("DEXCT_CONE_KB");
-    const bool kb4 = !(ke && atoi(ke) == 8);
-#define DEXCT_CONE_COLS_LAUNCH(NM_, CB_) \
-    do { \
-      if (kb4) hipLaunchKernelGGL((cone_cols_kernel<NM_, 4, CB_>), dim3((unsigned)nblk), dim3(kConeRows), 0, st, a, vol_zc, mu, weights, weights2, n_chunks, view_tile); \
-      else hipLaunchKernelGGL((cone_cols_kernel<NM_, 8, CB_>), dim3((unsigned)nblk), dim3(kConeRows), 0, st, a, vol_zc, mu, weights, weights2, n_chunks, view_tile); \
-    } while (0)
-    if (zs <= 288u) {
-      switch (nm) {
-        case 1: DEXCT_CONE_COLS_LAUNCH(1, 288); break;
-        case 2: DEXCT_CONE_COLS_LAUNCH(2, 288); break;
-        default: DEXCT_CONE_COLS_LAUNCH(3, 288); break;
-      }
-    } else if (zs <= 544u) {
-      switch (nm) {
-        case 1: DEXCT_CONE_COLS_LAUNCH(1, 544); break;
-        case 2: DEXCT_CONE_COLS_LAUNCH(2, 544); break;
-        default: DEXCT_CONE_COLS_LAUNCH(3, 544); break;
-      }
-    } else {                                   // up to 1024 slices: 4 slabs per batch only (17 KB of LDS per buffer)
-      switch (nm) {
-        case 1: hipLaunchKernelGGL((cone_cols_kernel<1, 4, 1056>), dim3((unsigned)nblk), dim3(kConeRows), 0, st, a, vol_zc, mu, weights, weights2, n_chunks, view_tile); break;
-        case 2: hipLaunchKernelGGL((cone_cols_kernel<2, 4, 1056>), dim3((unsigned)nblk), dim3(kConeRows), 0, st, a, vol_zc, mu, weights, weights2, n_chunks, view_tile); break;
-        default: hipLaunchKernelGGL((cone_cols_kernel<3, 4, 1056>), dim3((unsigned)nblk), dim3(kConeRows), 0, st, a, vol_zc, mu, weights, weights2, n_chunks, view_tile); break;
-      }
-    }
-#undef DEXCT_CONE_COLS_LAUNCH
+static int launch_cone_rows(const ConeArgs& a, const uint8_t* vol_zc, int nm, const Tables& t, hipStream_t st) {
+  using namespace proj;
+  const int n_chunks = (a.g.n_rows + kConeRows - 1) / kConeRows;
+  dim3 grid;
+  if (!grid_1d((size_t)a.n_local_views * a.g.n_channels * n_chunks, grid)) return DEXCT_ERANGE;
+  const int view_tile = read_knob(knob::kConeViewTile);
+  auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(kConeRows), 0, st, a, vol_zc, t.mu, t.w, t.w2, n_chunks, view_tile);
     DEXCT_LAUNCH_CHECK();
     return DEXCT_OK;
+  };
+  const uint32_t zs = cone_zs(a.g.nz);
+  if (read_knob(knob::kConeCols) != 0 && zs <= 1056u) {
+    const bool kb4 = read_knob(knob::kConeKb) != 8;
+    auto cols = [&](auto cb) {                 // CB: the bytes of a column the kernel reserves
+      constexpr int CB = decltype(cb)::value;
+      return for_materials<1, 2, 3>(nm, [&](auto m) {
+        constexpr int NM = decltype(m)::value;
+        if constexpr (CB > 544) return launch(cone_cols_kernel<NM, 4, CB>);     // up to 1024 slices: 4 slabs per batch only (17 KB of LDS per buffer)
+        else return kb4 ? launch(cone_cols_kernel<NM, 4, CB>) : launch(cone_cols_kernel<NM, 8, CB>);
+      });
+    };
+    if (zs <= 288u) return cols(std::integral_constant<int, 288>{});
+    if (zs <= 544u) return cols(std::integral_constant<int, 544>{});
+    return cols(std::integral_constant<int, 1056>{});
   }
-  switch (nm) {
-    case 1: hipLaunchKernelGGL(cone_rows_kernel<1>, dim3((unsigned)nblk), dim3(kConeRows), 0, st, a, vol_zc, mu, weights, weights2, n_chunks, view_tile); break;
-    case 2: hipLaunchKernelGGL(cone_rows_kernel<2>, dim3((unsigned)nblk), dim3(kConeRows), 0, st, a, vol_zc, mu, weights, weights2, n_chunks, view_tile); break;
-    default: {
-      const char* e = getenv("DEXCT_CONE_BATCH");         // tuning knob
-      const int kb = e ? atoi(e) : 4;
-      const char* le = getenv("DEXCT_CONE_LDSC");         // 0: corrections in registers (the round-2 form), for A/B
-      if (le && atoi(le) == 0) hipLaunchKernelGGL((cone_rows_kernel<3, 4, false>), dim3((unsigned)nblk), dim3(kConeRows), 0, st, a, vol_zc, mu, weights, weights2, n_chunks, view_tile);
-      else if (kb == 8) hipLaunchKernelGGL((cone_rows_kernel<3, 8>), dim3((unsigned)nblk), dim3(kConeRows), 0, st, a, vol_zc, mu, weights, weights2, n_chunks, view_tile);
-      else if (kb == 2) hipLaunchKernelGGL((cone_rows_kernel<3, 2>), dim3((unsigned)nblk), dim3(kConeRows), 0, st, a, vol_zc, mu, weights, weights2, n_chunks, view_tile);
-      else hipLaunchKernelGGL((cone_rows_kernel<3, 4>), dim3((unsigned)nblk), dim3(kConeRows), 0, st, a, vol_zc, mu, weights, weights2, n_chunks, view_tile);
-      break;
+  return for_materials<1, 2, 3>(nm, [&](auto m) {
+    constexpr int NM = decltype(m)::value;
+    if constexpr (NM < 3) return launch(cone_rows_kernel<NM>);
+    else {
+      if (read_knob(knob::kConeLdsc) == 0) return launch(cone_rows_kernel<3, 4, false>);
+      const int kb = read_knob(knob::kConeBatch);
+      return kb == 8 ? launch(cone_rows_kernel<3, 8>) : kb == 2 ? launch(cone_rows_kernel<3, 2>) : launch(cone_rows_kernel<3, 4>);
     }
-  }
-  DEXCT_LAUNCH_CHECK();
-  return DEXCT_OK;
+  });
 }
 
-static void fill_cone_args(ConeArgs& a, const dexct_fan_geom* geom, const dexct_ray_plan* plan, const double* view_cs,
-                           const double* chan_cs, const double* row_z, double src_z, int32_t view_begin, int32_t view_end,
-                           int32_t n_materials, int32_t n_energies, int32_t n_spectra, float* counts, float* pathlen,
-                           const dexct_log_out* log_out) {
-  a.g = *geom;
-  a.plan = plan;
-  a.view_cs = view_cs;
-  a.chan_cs = chan_cs;
-  a.row_z = row_z;
-  a.src_z = src_z;
-  a.vol_yx = nullptr;
-  a.vol_xy = nullptr;
-  a.view_begin = view_begin;
-  a.n_local_views = view_end - view_begin;
-  a.n_materials = n_materials;
-  a.n_energies = n_energies;
-  a.n_spectra = n_spectra;
-  a.counts = counts;
-  a.pathlen = pathlen;
-  a.sino_log = log_out ? log_out->sino_log : nullptr;
-  for (int s = 0; s < DEXCT_MAX_SPECTRA; ++s) a.air[s] = log_out ? log_out->air[s] : 1.0f;
-}
+}  // namespace dexct
 
 extern "C" int dexct_cone_project_rows(const dexct_fan_geom* geom, const dexct_ray_plan* plan, const double* view_cs,
                                        const double* chan_cs, const double* row_z, double src_z, double max_abs_dz,
@@ -1003,16 +938,15 @@ extern "C" int dexct_cone_project_rows(const dexct_fan_geom* geom, const dexct_r
                                        const dexct_log_out* log_out, const float* weights2, float* variance,
                                        const dexct_noise* noise, void* stream) {
   if (!geom || !plan || !view_cs || !chan_cs || !row_z || !vol_zc || !mu || !weights || !counts) return DEXCT_EINVAL;
-  if (cone_noise_args(weights2, variance, noise, log_out) != DEXCT_OK) return DEXCT_EINVAL;
+  const proj::NoiseLog nl = proj::noise_log_args(weights2, variance, noise, log_out, n_spectra, n_materials, proj::NoiseBy::kOwnLoop);
+  if (nl.status() != DEXCT_OK) return nl.status();
   if (n_materials < 1) return DEXCT_EINVAL;
   if (n_materials > 3) return DEXCT_ERANGE;      // code 3 is "outside the grid" (more: dexct_cone_project_grouped)
   const int rc = cone_rows_checks(geom, view_begin, view_end, n_energies, n_spectra, max_abs_dz);
   if (rc != DEXCT_OK) return rc;
-  ConeArgs a;
-  fill_cone_args(a, geom, plan, view_cs, chan_cs, row_z, src_z, view_begin, view_end, n_materials, n_energies, n_spectra, counts,
-                 pathlen, log_out);
-  set_cone_noise(a, variance, noise);
-  return launch_cone_rows(a, vol_zc, n_materials, mu, weights, weights2, as_stream(stream));
+  const ConeArgs a = fill_cone_args(*geom, plan, view_cs, chan_cs, row_z, src_z, view_begin, view_end, n_materials, n_energies,
+                                    n_spectra, counts, pathlen, variance, nl);
+  return launch_cone_rows(a, vol_zc, n_materials, Tables{mu, weights, weights2}, as_stream(stream));
 }
 
 extern "C" int dexct_cone_layout_groups(const uint8_t* vol, int32_t nx, int32_t ny, int32_t nz, int32_t n_materials,
@@ -1021,10 +955,9 @@ extern "C" int dexct_cone_layout_groups(const uint8_t* vol, int32_t nx, int32_t 
   if (n_materials < 1 || n_materials > DEXCT_MAX_MATERIALS) return DEXCT_ERANGE;
   const int64_t total = dexct_cone_layout_bytes(nx, ny, nz);
   if (total > 0xFFFFFFFEll) return DEXCT_ERANGE;
-  const int n_groups = (n_materials + 2) / 3;
   const int64_t nblk = (total + 255) / 256;
-  hipLaunchKernelGGL(cone_layout_groups_kernel, dim3((unsigned)nblk), dim3(256), 0, as_stream(stream), vol, nx, ny, nz, n_groups,
-                     vol_zcg);
+  hipLaunchKernelGGL(cone_layout_groups_kernel, dim3((unsigned)nblk), dim3(256), 0, as_stream(stream), vol, nx, ny, nz,
+                     proj::n_groups(n_materials, false), vol_zcg);
   DEXCT_LAUNCH_CHECK();
   return DEXCT_OK;
 }
@@ -1040,41 +973,27 @@ extern "C" int dexct_cone_project_grouped(const dexct_fan_geom* geom, const dexc
   if (n_materials > DEXCT_MAX_MATERIALS) return DEXCT_ERANGE;
   const int rc = cone_rows_checks(geom, view_begin, view_end, n_energies, n_spectra, max_abs_dz);
   if (rc != DEXCT_OK) return rc;
-  // ---- the arguments of the detection pass first: a refused call (noise / log combination) must have launched nothing
-  ProjArgs d;
-  d.g = *geom;
-  d.plan = plan;
-  d.vol_yx = d.vol_xy = d.vol_zf = nullptr;
-  d.n_local_views = view_end - view_begin;
-  d.n_materials = n_materials;
-  d.n_energies = n_energies;
-  d.n_spectra = n_spectra;
-  d.counts = counts;
-  d.pathlen = pathlen;
-  d.variance = variance;
-  d.view_tile = 1;
-  d.layout = 0;
-  d.acc_out = acc_scratch;
-  d.mat_base = 0;
-  d.acc_lengths = 1;
-  { const int nrc = set_noise(d, view_begin, weights2, variance, noise); if (nrc != DEXCT_OK) return nrc; }
-  if (set_log_out(d, log_out, d.sample ? nullptr : variance) != DEXCT_OK) return DEXCT_EINVAL;
+  // ---- the noise / log rule of the detection pass first: a refused call must have launched nothing
+  const proj::NoiseLog nl = proj::noise_log_args(weights2, variance, noise, log_out, n_spectra, n_materials, proj::NoiseBy::kGroupPass);
+  if (nl.status() != DEXCT_OK) return nl.status();
   hipStream_t st = as_stream(stream);
-  // ---- one traversal per group of three materials: lengths [cm] into the planes of acc_scratch
-  ConeArgs a;
-  fill_cone_args(a, geom, plan, view_cs, chan_cs, row_z, src_z, view_begin, view_end, n_materials, n_energies, n_spectra, counts,
-                 nullptr, nullptr);
-  set_cone_noise(a, nullptr, nullptr);
+  // ---- one traversal per group of three materials: lengths [cm] into the planes of acc_scratch; no detection, no tables' w2
+  ConeArgs a = fill_cone_args(*geom, plan, view_cs, chan_cs, row_z, src_z, view_begin, view_end, n_materials, n_energies, n_spectra,
+                              counts, nullptr, nullptr, proj::NoiseLog{});
   a.acc_out = acc_scratch;
   const size_t layout_bytes = (size_t)dexct_cone_layout_bytes(geom->nx, geom->ny, geom->nz);
-  const int n_groups = (n_materials + 2) / 3;
-  for (int g = 0; g < n_groups; ++g) {
+  for (int g = 0; g < proj::n_groups(n_materials, false); ++g) {
     a.mat_base = 3 * g;
-    const int left = n_materials - 3 * g;
-    const int lrc = launch_cone_rows(a, vol_zcg + (size_t)g * layout_bytes, left >= 3 ? 3 : left, mu, weights, nullptr, st);
+    const int lrc = launch_cone_rows(a, vol_zcg + (size_t)g * layout_bytes, proj::group_size(n_materials, false, g),
+                                     Tables{mu, weights, nullptr}, st);
     if (lrc != DEXCT_OK) return lrc;
   }
   // ---- one detection pass over all planes (the pass of the stacked fan's material groups, reading lengths)
-  const Tables t{mu, weights, weights2};
-  return launch_detect_any(d, t, st);
+  ProjArgs d = proj::fill_proj_args(*geom, plan, view_begin, view_end, n_materials, n_energies, n_spectra, counts, pathlen, variance,
+                                    0, nl);
+  proj::copy_noise(d, view_begin, nl);
+  d.view_tile = 1;
+  d.acc_out = acc_scratch;
+  d.acc_lengths = 1;
+  return launch_detect_any(d, Tables{mu, weights, weights2}, st);
 }

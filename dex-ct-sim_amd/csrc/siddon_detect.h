@@ -48,38 +48,6 @@ struct ProjArgs {
   float air[DEXCT_MAX_SPECTRA];
 };
 
-// log_out of the C ABI -> launch arguments (null: no log sinogram).  With a variance output the log belongs to the noisy
-// counts, which only exist after dexct_add_noise: the caller then uses dexct_sino_log (`variance` non-null here = "the counts
-// this launch writes are not the final ones"; a kernel that samples the noise itself passes null).
-// the noise arguments of the group entry points -> launch arguments; DEXCT_EINVAL for a combination that makes no sense
-inline int set_noise(ProjArgs& a, int32_t view_begin, const float* weights2, const float* variance, const dexct_noise* noise) {
-  const bool sample = noise && noise->sample;
-  a.view_begin = view_begin;
-  a.sample = 0;
-  a.seed_lo = a.seed_hi = 0u;
-  if (!weights2) return (variance || sample) ? DEXCT_EINVAL : DEXCT_OK;
-  if (!variance && !sample) return DEXCT_EINVAL;
-  if (sample) {
-    // (the fused variance: two spectrum slots, register lengths; a single material goes to detect_kernel_chunked, which draws
-    // no sample - only dexct_cone_project_grouped admits one material at all)
-    if (a.n_spectra > 2 || a.n_materials > 48 || a.n_materials < 2) return DEXCT_ERANGE;
-    a.sample = 1;
-    a.seed_lo = (uint32_t)noise->seed;
-    a.seed_hi = (uint32_t)(noise->seed >> 32);
-  }
-  return DEXCT_OK;
-}
-
-inline int set_log_out(ProjArgs& a, const dexct_log_out* lo, const float* variance) {
-  a.sino_log = nullptr;
-  for (int s = 0; s < DEXCT_MAX_SPECTRA; ++s) a.air[s] = 1.0f;
-  if (!lo || !lo->sino_log) return DEXCT_OK;
-  if (variance) return DEXCT_EINVAL;
-  a.sino_log = lo->sino_log;
-  for (int s = 0; s < DEXCT_MAX_SPECTRA; ++s) a.air[s] = lo->air[s];
-  return DEXCT_OK;
-}
-
 // launch arguments of rows16_kernel (siddon_packed.hip): the 2-bit packed volume
 struct PackedArgs {
   ProjArgs a;
@@ -105,7 +73,7 @@ struct Tables {
   const float* __restrict__ w2;   // [S][nE] w * signal per photon (variance weights), or null
 };
 
-// detection of the material-major accumulator planes a group pass leaves in a.acc_out (siddon.hip; any material count)
+// detection of the material-major accumulator planes a group pass leaves in a.acc_out (detect.hip; any material count)
 int launch_detect_any(const ProjArgs& a, const Tables& t, hipStream_t st);
 
 __device__ __forceinline__ size_t ray_index(const ProjArgs& a, int v, int r, int c) {

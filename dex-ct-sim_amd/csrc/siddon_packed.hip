@@ -20,11 +20,9 @@
 // Lanes: a pair of n_rows rows needs n_rows / 16 lanes.  For n_rows / 16 < 64 a wave carries 64 / (n_rows / 16)
 // neighbouring channels of one view (per-lane pair index; each pair has its own slab lists in LDS and list entries
 // beyond a pair's count point outside the buffer, which reads as air and counts nothing).
-#include <cstdlib>
-
 #include "common.h"
 #include "noise_sample.h"
-#include "siddon_detect.h"
+#include "proj_host.h"
 
 namespace dexct {
 
@@ -492,31 +490,44 @@ __global__ __launch_bounds__(256) void group_codes_pack2_kernel(const uint8_t* _
   }
 }
 
-// what both entry points check; fills the launch shape
+// one launch of rows16_kernel
+struct P16Launch {
+  PackedArgs pa;
+  Tables t;
+  dim3 grid;
+  size_t lds;
+  hipStream_t st;
+};
+template <int NM, int MINW, bool GROUPED, bool STAGED, bool NOISY>
+static int launch_p16(const P16Launch& l) {
+  hipLaunchKernelGGL((rows16_kernel<NM, MINW, GROUPED, STAGED, NOISY>), l.grid, dim3(64), l.lds, l.st, l.pa, l.t.mu, l.t.w, l.t.w2);
+  DEXCT_LAUNCH_CHECK();
+  return DEXCT_OK;
+}
+
+// what both entry points check, in this order; fills the launch shape
 static int packed_shape(const dexct_fan_geom* geom, int32_t view_begin, int32_t view_end, int32_t layout, PackedArgs& pa,
-                        size_t& nblk, size_t& lds) {
-  if (view_begin < 0 || view_end > geom->n_views || view_end <= view_begin) return DEXCT_EINVAL;
+                        dim3& grid, size_t& lds) {
+  if (!proj::views_ok(*geom, view_begin, view_end)) return DEXCT_EINVAL;
   if (geom->n_rows < 1) return DEXCT_EINVAL;
-  if (geom->z_first < 0 || geom->z_first + geom->n_rows > geom->nz) return DEXCT_EINVAL;
-  if (geom->nz % 16 != 0 || geom->z_first % 16 != 0) return DEXCT_EINVAL;
-  if ((uint64_t)geom->nx * geom->ny * (geom->nz / 4) > 0xEFFF0000ull) return DEXCT_ERANGE;     // below kOob
+  if (!proj::stack_ok(*geom)) return DEXCT_EINVAL;
+  if (!proj::stack_aligned(*geom, 16)) return DEXCT_EINVAL;
+  if (!proj::offsets_fit(*geom, 4, 0xEFFF0000ull)) return DEXCT_ERANGE;    // below kOob
   if (geom->nx > 2047 || geom->ny > 2047) return DEXCT_ERANGE;             // 11-bit sliced counters: one count per slab
-  if (layout != 0 && layout != 1) return DEXCT_EINVAL;
-  if (geom->n_rows > 65535 || view_end - view_begin > 65535) return DEXCT_ERANGE;
+  if (!proj::layout_ok(layout)) return DEXCT_EINVAL;
+  if (!proj::fits_16bit(*geom, view_begin, view_end)) return DEXCT_ERANGE;
   // a (view, channel) pair takes ceil(n_rows / 16) lanes: 16 or 32 lanes per pair (4 or 2 pairs per wave) or whole
   // waves; lanes past the last row idle (the caller decides whether that is still worth it)
   const int lanes = (geom->n_rows + 15) / 16;
   pa.lanes_per_pair = lanes > 32 ? 64 : (lanes > 16 ? 32 : 16);
   pa.n_zchunks = lanes > 64 ? (lanes + 63) / 64 : 1;
-  pa.view_tile = 16;                 // (8 until round 5: 16 measured 2 - 4 % faster on every stacked-fan configuration, tools/probes/p16_knobs.py)
-  pa.det_masks = 1;
-  if (const char* e = getenv("DEXCT_DET_MASKS")) pa.det_masks = atoi(e) != 0;
-  pa.staged_store = 1;
-  if (const char* e = getenv("DEXCT_P16_STAGED")) pa.staged_store = atoi(e) != 0;
-  if (const char* e = getenv("DEXCT_VIEW_TILE")) { const int t = atoi(e); if (t >= 1 && t <= 4096) pa.view_tile = t; }
+  pa.view_tile = proj::read_knob(proj::knob::kViewTileP16);
+  pa.det_masks = proj::read_knob(proj::knob::kDetMasks) != 0;
+  pa.staged_store = proj::read_knob(proj::knob::kP16Staged) != 0;
+  pa.view_begin = view_begin;
   const int n_pairs = 64 / pa.lanes_per_pair;
-  nblk = (size_t)(view_end - view_begin) * ((geom->n_channels + n_pairs - 1) / n_pairs) * pa.n_zchunks;
-  if (nblk > 0x7FFFFFFFull) return DEXCT_ERANGE;
+  if (!proj::grid_1d((size_t)(view_end - view_begin) * ((geom->n_channels + n_pairs - 1) / n_pairs) * pa.n_zchunks, grid))
+    return DEXCT_ERANGE;
   lds = (size_t)n_pairs * kP16Super * (sizeof(CrossRec) + sizeof(uint32_t));
   if (lds < 2 * 64 * 64) lds = 2 * 64 * 64;   // the staged store of the results: 64 bytes per lane and spectrum
   return DEXCT_OK;
@@ -531,9 +542,9 @@ extern "C" {
 int dexct_volume_pack2(const uint8_t* vol_zf, int64_t n_voxels, uint8_t* vol_z2, void* stream) {
   if (!vol_zf || !vol_z2 || n_voxels <= 0 || (n_voxels & 3)) return DEXCT_EINVAL;
   const size_t nb = (size_t)n_voxels / 4;
-  const size_t nblk = (nb + 255) / 256;
-  if (nblk > 0x7FFFFFFFull) return DEXCT_ERANGE;
-  hipLaunchKernelGGL(pack2_kernel, dim3((unsigned)nblk), dim3(256), 0, as_stream(stream), vol_zf, nb, vol_z2);
+  dim3 grid;
+  if (!proj::grid_1d((nb + 255) / 256, grid)) return DEXCT_ERANGE;
+  hipLaunchKernelGGL(pack2_kernel, grid, dim3(256), 0, as_stream(stream), vol_zf, nb, vol_z2);
   DEXCT_LAUNCH_CHECK();
   return DEXCT_OK;
 }
@@ -541,11 +552,10 @@ int dexct_volume_pack2(const uint8_t* vol_zf, int64_t n_voxels, uint8_t* vol_z2,
 int dexct_volume_groups_pack2(const uint8_t* vol_zf, int64_t n_voxels, int32_t n_materials, uint8_t* codes2, void* stream) {
   if (!vol_zf || !codes2 || n_voxels <= 0 || (n_voxels & 3)) return DEXCT_EINVAL;
   if (n_materials < 2 || n_materials > DEXCT_MAX_MATERIALS) return DEXCT_ERANGE;
-  const int n_groups = (n_materials - 1 + 2) / 3;
   const size_t nb = (size_t)n_voxels / 4;
-  const size_t nblk = (nb + 255) / 256;
-  if (nblk > 0x7FFFFFFFull) return DEXCT_ERANGE;
-  hipLaunchKernelGGL(group_codes_pack2_kernel, dim3((unsigned)nblk), dim3(256), 0, as_stream(stream), vol_zf, nb, n_groups,
+  dim3 grid;
+  if (!proj::grid_1d((nb + 255) / 256, grid)) return DEXCT_ERANGE;
+  hipLaunchKernelGGL(group_codes_pack2_kernel, grid, dim3(256), 0, as_stream(stream), vol_zf, nb, proj::n_groups(n_materials, true),
                      codes2);
   DEXCT_LAUNCH_CHECK();
   return DEXCT_OK;
@@ -559,85 +569,40 @@ int dexct_siddon_project_packed(const dexct_fan_geom* geom, const dexct_ray_plan
   if (!geom || !plan || !vol_z2 || !mu || !weights || !counts) return DEXCT_EINVAL;
   if (n_energies < 1 || n_spectra < 1) return DEXCT_EINVAL;
   if (n_materials < 2 || n_materials > 4 || n_spectra > DEXCT_MAX_SPECTRA) return DEXCT_ERANGE;     // ids 0..3
-  // quantum noise: weights2 switches the variance on; it then needs somewhere to go - the optional output, the sample, or both
-  const bool sample = noise && noise->sample;
-  const bool noisy = weights2 != nullptr;
-  if (!noisy && (variance || sample)) return DEXCT_EINVAL;
-  if (noisy && !variance && !sample) return DEXCT_EINVAL;
-  if (noisy && n_spectra > 2) return DEXCT_ERANGE;              // (the fused variance runs in the two-slot detection)
-  PackedArgs pa;
-  size_t nblk, lds;
-  const int rc = packed_shape(geom, view_begin, view_end, layout, pa, nblk, lds);
+  const proj::NoiseLog nl = proj::noise_log_args(weights2, variance, noise, log_out, n_spectra, n_materials, proj::NoiseBy::kTwoSlots);
+  if (nl.noise_rc != DEXCT_OK) return nl.noise_rc;
+  P16Launch l{};
+  const int rc = packed_shape(geom, view_begin, view_end, layout, l.pa, l.grid, l.lds);
   if (rc != DEXCT_OK) return rc;
-  ProjArgs& a = pa.a;
-  a.g = *geom;
-  a.plan = plan;
-  a.vol_yx = nullptr;
-  a.vol_xy = nullptr;
-  a.vol_zf = nullptr;
-  a.n_local_views = view_end - view_begin;
-  a.n_materials = n_materials;
-  a.n_energies = n_energies;
-  a.n_spectra = n_spectra;
-  a.counts = counts;
-  a.pathlen = pathlen;
-  a.variance = variance;
-  a.acc_out = nullptr;
-  a.mat_base = 0;
-  a.layout = layout;
-  // the log of a noisy sinogram is the log of the SAMPLED counts: the kernel writes it only when it draws the sample itself
-  if (set_log_out(a, log_out, (noisy && !sample) ? weights2 : nullptr) != DEXCT_OK) return DEXCT_EINVAL;
-  a.view_tile = pa.view_tile;
-  pa.vol_z2 = vol_z2;
-  pa.view_begin = view_begin;
-  pa.sample = sample ? 1 : 0;
-  pa.seed_lo = sample ? (uint32_t)noise->seed : 0u;
-  pa.seed_hi = sample ? (uint32_t)(noise->seed >> 32) : 0u;
-  hipStream_t st = as_stream(stream);
-  int minw = 4;
-  if (const char* e = getenv("DEXCT_P16_MINW")) minw = atoi(e);      // tuning knob
-  const float* none = nullptr;
+  if (nl.log_rc != DEXCT_OK) return nl.log_rc;
+  l.pa.a = proj::fill_proj_args(*geom, plan, view_begin, view_end, n_materials, n_energies, n_spectra, counts, pathlen, variance, layout,
+                                nl);
+  l.pa.a.view_tile = l.pa.view_tile;
+  l.pa.vol_z2 = vol_z2;
+  proj::copy_noise(l.pa, view_begin, nl);      // (rows16_kernel draws the sample itself: PackedArgs, not its ProjArgs)
+  l.t = Tables{mu, weights, weights2};
+  l.st = as_stream(stream);
+  const bool noisy = weights2 != nullptr;
   // whole-line stores through LDS (STAGED) wherever the output allows them: row-fastest layout, whole groups of 4 rows,
   // one or two spectra (what the stage holds)
-  const bool staged = pa.staged_store && layout == 1 && geom->n_rows % 4 == 0 && n_spectra <= 2;
+  const bool staged = l.pa.staged_store && layout == 1 && geom->n_rows % 4 == 0 && n_spectra <= 2;
+  // rows16_kernel<NM, MINW, false, STAGED, NOISY>: MINW is 4 for two and three materials, 3 for four.  (The order of the arms
+  // is the order in which the kernels are instantiated, hence their order in the code object.)
   if (noisy) {
-    if (n_materials == 2 && staged)
-      hipLaunchKernelGGL((rows16_kernel<2, 4, false, true, true>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, weights2);
-    else if (n_materials == 2)
-      hipLaunchKernelGGL((rows16_kernel<2, 4, false, false, true>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, weights2);
-    else if (n_materials == 4 && staged)
-      hipLaunchKernelGGL((rows16_kernel<4, 3, false, true, true>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, weights2);
-    else if (n_materials == 4)
-      hipLaunchKernelGGL((rows16_kernel<4, 3, false, false, true>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, weights2);
-    else if (staged)
-      hipLaunchKernelGGL((rows16_kernel<3, 4, false, true, true>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, weights2);
-    else
-      hipLaunchKernelGGL((rows16_kernel<3, 4, false, false, true>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, weights2);
-    DEXCT_LAUNCH_CHECK();
-    return DEXCT_OK;
+    if (n_materials == 2) return staged ? launch_p16<2, 4, false, true, true>(l) : launch_p16<2, 4, false, false, true>(l);
+    if (n_materials == 4) return staged ? launch_p16<4, 3, false, true, true>(l) : launch_p16<4, 3, false, false, true>(l);
+    return staged ? launch_p16<3, 4, false, true, true>(l) : launch_p16<3, 4, false, false, true>(l);
   }
-  if (n_materials == 2 && staged)
-    hipLaunchKernelGGL((rows16_kernel<2, 4, false, true>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, none);
-  else if (n_materials == 2)
-    hipLaunchKernelGGL((rows16_kernel<2>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, none);
-  else if (n_materials == 4 && staged)
-    hipLaunchKernelGGL((rows16_kernel<4, 3, false, true>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, none);
-  else if (n_materials == 4)
-    hipLaunchKernelGGL((rows16_kernel<4, 3>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, none);
-  else if (staged && minw == 4)
-    hipLaunchKernelGGL((rows16_kernel<3, 4, false, true>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, none);
-  else if (staged && minw == 5)
-    hipLaunchKernelGGL((rows16_kernel<3, 5, false, true>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, none);
-  else if (minw == 5)
-    hipLaunchKernelGGL((rows16_kernel<3, 5>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, none);
-  else if (minw == 6)
-    hipLaunchKernelGGL((rows16_kernel<3, 6>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, none);
-  else if (minw == 8)
-    hipLaunchKernelGGL((rows16_kernel<3, 8>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, none);
-  else
-    hipLaunchKernelGGL((rows16_kernel<3>), dim3((unsigned)nblk), dim3(64), lds, st, pa, mu, weights, none);
-  DEXCT_LAUNCH_CHECK();
-  return DEXCT_OK;
+  if (n_materials == 2) return staged ? launch_p16<2, 4, false, true, false>(l) : launch_p16<2, 4, false, false, false>(l);
+  if (n_materials == 4) return staged ? launch_p16<4, 3, false, true, false>(l) : launch_p16<4, 3, false, false, false>(l);
+  // three materials without noise also have the forms DEXCT_P16_MINW asks for: 5 with and without the staged store, 6 and 8
+  // without; every other value is 4 - and any value but 4 and 5 has always cost the staged store
+  const int minw = proj::read_knob(proj::knob::kP16MinW);
+  if (staged && minw == 4) return launch_p16<3, 4, false, true, false>(l);
+  if (minw == 5) return staged ? launch_p16<3, 5, false, true, false>(l) : launch_p16<3, 5, false, false, false>(l);
+  if (minw == 6) return launch_p16<3, 6, false, false, false>(l);
+  if (minw == 8) return launch_p16<3, 8, false, false, false>(l);
+  return launch_p16<3, 4, false, false, false>(l);
 }
 
 int dexct_siddon_project_grouped_packed(const dexct_fan_geom* geom, const dexct_ray_plan* plan, int32_t view_begin,
@@ -648,50 +613,29 @@ int dexct_siddon_project_grouped_packed(const dexct_fan_geom* geom, const dexct_
   if (!geom || !plan || !codes2 || !mu || !weights || !counts || !acc_scratch) return DEXCT_EINVAL;
   if (n_materials < 2 || n_energies < 1 || n_spectra < 1) return DEXCT_EINVAL;
   if (n_materials > DEXCT_MAX_MATERIALS || n_spectra > DEXCT_MAX_SPECTRA) return DEXCT_ERANGE;
-  PackedArgs pa;
-  size_t nblk, lds;
-  const int rc = packed_shape(geom, view_begin, view_end, layout, pa, nblk, lds);
+  P16Launch l{};
+  const int rc = packed_shape(geom, view_begin, view_end, layout, l.pa, l.grid, l.lds);
   if (rc != DEXCT_OK) return rc;
-  ProjArgs& a = pa.a;
-  a.g = *geom;
-  a.plan = plan;
-  a.vol_yx = nullptr;
-  a.vol_xy = nullptr;
-  a.vol_zf = nullptr;
-  a.n_local_views = view_end - view_begin;
-  a.n_materials = n_materials;
-  a.n_energies = n_energies;
-  a.n_spectra = n_spectra;
-  a.counts = counts;
-  a.pathlen = pathlen;
-  a.variance = variance;
+  const proj::NoiseLog nl = proj::noise_log_args(weights2, variance, noise, log_out, n_spectra, n_materials, proj::NoiseBy::kGroupPass);
+  if (nl.status() != DEXCT_OK) return nl.status();
+  ProjArgs& a = l.pa.a;
+  a = proj::fill_proj_args(*geom, plan, view_begin, view_end, n_materials, n_energies, n_spectra, counts, pathlen, variance, layout, nl);
+  proj::copy_noise(a, view_begin, nl);          // (the detection pass draws the sample, not rows16_kernel)
   a.acc_out = acc_scratch;
-  a.mat_base = 0;
-  a.layout = layout;
-  { const int nrc = set_noise(a, view_begin, weights2, variance, noise); if (nrc != DEXCT_OK) return nrc; }
-  if (set_log_out(a, log_out, a.sample ? nullptr : variance) != DEXCT_OK) return DEXCT_EINVAL;
-  a.view_tile = pa.view_tile;
-  pa.view_begin = view_begin;
-  pa.sample = 0;
-  pa.seed_lo = pa.seed_hi = 0u;
-  hipStream_t st = as_stream(stream);
+  a.view_tile = l.pa.view_tile;
+  l.st = as_stream(stream);                     // (the group passes take no tables: l.t stays null)
   const size_t group_bytes = (size_t)geom->nx * geom->ny * (geom->nz / 4);
-  const int n_groups = (n_materials - 1 + 2) / 3;
-  const float* none = nullptr;
-  for (int g = 0; g < n_groups; ++g) {
-    pa.vol_z2 = codes2 + (size_t)g * group_bytes;
+  for (int g = 0; g < proj::n_groups(n_materials, true); ++g) {
+    l.pa.vol_z2 = codes2 + (size_t)g * group_bytes;
     a.mat_base = 3 * g;
-    const int left = n_materials - 1 - 3 * g;           // materials in this group: 1..3
-    if (left >= 3)
-      hipLaunchKernelGGL((rows16_kernel<4, 3, true>), dim3((unsigned)nblk), dim3(64), lds, st, pa, none, none, none);
-    else if (left == 2)
-      hipLaunchKernelGGL((rows16_kernel<3, 4, true>), dim3((unsigned)nblk), dim3(64), lds, st, pa, none, none, none);
-    else
-      hipLaunchKernelGGL((rows16_kernel<2, 4, true>), dim3((unsigned)nblk), dim3(64), lds, st, pa, none, none, none);
-    DEXCT_LAUNCH_CHECK();
+    // (codes 0..3 of a group: its materials and "none of them")
+    const int lrc = proj::for_materials<4, 3, 2>(proj::group_size(n_materials, true, g) + 1, [&](auto nm) {
+      constexpr int NM = decltype(nm)::value;
+      return launch_p16<NM, (NM == 4 ? 3 : 4), true, false, false>(l);
+    });
+    if (lrc != DEXCT_OK) return lrc;
   }
-  const Tables t{mu, weights, weights2};
-  return launch_detect_any(a, t, st);
+  return launch_detect_any(a, Tables{mu, weights, weights2}, l.st);
 }
 
 }  // extern "C"

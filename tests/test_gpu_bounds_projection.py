@@ -35,8 +35,8 @@ Kernel (__global__) -> test that launches it
                  rows4_kernel<NM, B, false>               test_siddon_project[kernel 3] (B = 64; 128 and 256 lanes: r257 / r1100 rows)
                  rows4_kernel<NM, B, true>                test_material_counts[grouped], test_grouped_options
                  rows4t_kernel<NM, 8, 64, false>          test_siddon_project[kernel 5]
-                 rows4t_kernel<.., true>                  NOT REACHED: no entry point passes acc_out to kernel 5 (launch_rows4t's
-                                                          group branch has no caller)
+                 rows4t_kernel<.., true>                  not instantiated: no entry point passes acc_out to kernel 5, and
+                                                          launch_rows4t has no group branch any more
                  wave_ray_kernel<1..4>                    test_siddon_project[kernel 6]
                  trace_kernel                             test_siddon_trace
   siddon_packed.hip  pack2_kernel, group_codes_pack2_kernel   test_volume_pack2, test_volume_groups_pack2
@@ -68,7 +68,7 @@ Outcome.  Reading for these tests found, and test_refused_calls_launch_nothing n
     arguments are built and checked before the first launch_cone_rows.
   * n_materials == 1 with noise->sample on dexct_cone_project_grouped (the only group entry point that admits one material)
     returned noise-free counts and DEXCT_OK, because detect_kernel_chunked draws no sample.  Decided: refused with DEXCT_ERANGE
-    (set_noise in siddon_detect.h; include/dexct.h says so); the variance output + dexct_add_noise remains.
+    (noise_log_args in csrc/proj_host.h; include/dexct.h says so); the variance output + dexct_add_noise remains.
 Record of the run on an MI355X: the 466 cases of the two modules take 6.4 s; the -m gpu suite without them (the parent's
 tests, run in the same visit on this library, not on a build of the parent commit) takes 252.6 s.  No guard changed, no
 output depended on a fill, dexct_last_hip_error() stayed 0 on every launch form listed above, every output element was written

@@ -7,7 +7,8 @@ source text owes: identical instruction streams need no benchmark.
     python tools/device_asm_diff.py --md <old> <new> gn_multi.hip                      # a markdown table
 
 Lines containing `__hip_cuid` are dropped: that symbol is a hash of the source text, the one thing that differs when code only
-moves.  Everything else - instructions, kernel descriptors, metadata - is compared as whole text.  Exit status 1 if anything
+moves; so is the ordinal a function's local labels carry (its position in the file: removing one instantiation renumbers every
+function behind it).  Everything else - instructions, kernel descriptors, metadata - is compared as whole text.  Exit status 1 if anything
 differs.
 """
 import difflib
@@ -35,16 +36,30 @@ def assembly(root, src):
     return [l for l in p.stdout.splitlines() if '__hip_cuid' not in l]
 
 
+# local labels carry the ordinal of their function in the file (.LBB35_12, .Lfunc_end35, "Header=BB35_1"): it changes for every
+# function behind one that was added or removed, and it says nothing about the function itself
+_ORDINAL = re.compile(r'(?<![A-Za-z0-9_])((?:\.L)?(?:BB|func_begin|func_end))\d+')
+
+
 def sections(lines):
-    """{name: lines}: the text before the first function, every function from its `.type name,@function` line to the next
-    one's (its kernel descriptor included), and the metadata note at the end."""
+    """{name: lines}: the text before the first function, every function from the directives that open its section (those
+    that name it, in front of its `.type name,@function` line) to the next one's (its kernel descriptor included), and the
+    metadata note at the end.  Function ordinals in local labels are blanked."""
     out, name = {'(preamble)': []}, '(preamble)'
     for l in lines:
         m = re.match(r'\s*\.type\s+([^,\s]+),@function', l)
         if m:
-            name = m.group(1)
+            prev, k = out[name], len(out[name])
+            while k > 0 and (m.group(1) in prev[k - 1] or re.match(r'\s*\.p2align', prev[k - 1])):
+                k -= 1
+            name, head = m.group(1), prev[k:]
+            del prev[k:]
+            out.setdefault(name, []).extend(head)
         elif re.match(r'\s*\.amdgpu_metadata', l):
             name = '(metadata)'
+        l = _ORDINAL.sub(r'\1#', l)
+        if l.startswith('.LBB'):       # a label line: the column of its comment moves with the number of digits
+            l = re.sub(r':\s+;', ': ;', l, count=1)
         out.setdefault(name, []).append(l)
     return out
 
