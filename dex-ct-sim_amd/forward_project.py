@@ -9,6 +9,7 @@ the weighting that the reference's decomposition assumes (matdecomp.py:146-150):
 
 All work runs in the HIP library (dexct_fan_plan, dexct_volume_layouts, dexct_siddon_project).
 """
+import collections
 import ctypes as C
 import os as _os
 
@@ -64,6 +65,35 @@ def compact_ids(present, materials):
     return mat_rows, lut
 
 
+# Where a projection kernel draws the noise sample itself: the limits proj::noise_log_args (csrc/proj_host.h) enforces
+# (Projector._samples_in_kernel is their one reader on this side)
+_NOISE_MAX_SPECTRA = 2          # the two slots of the packed stacked fan and of the groups' detection pass
+_NOISE_MAX_GROUP_ROWS = 48      # table rows up to which the groups' detection pass samples (kManyMaterials)
+
+# What Projector._launch needs of one project_tables call: the plan of its first view and that view's global number, the
+# tables (device pointers), the unattenuated signals of the log, the kernel's noise (None: it draws none), the layout it
+# writes, and whether the packed stacked fan serves this call
+_Call = collections.namedtuple('_Call', 'plan_ptr vb S nE mu w w2 air nz run_layout packed')
+
+
+def _in_view_chunks(launch, n_chunk, counts, pathlen, variance, log):
+    """``launch(v0, v1, counts, pathlen, variance, log)`` over all views of the outputs, ``n_chunk`` views at a time (the
+    view is dimension 1 of counts, variance and log, dimension 0 of pathlen; an output that is None stays None).  One chunk
+    that covers every view writes into the outputs themselves; otherwise each chunk gets outputs of its own size, which
+    are copied into place."""
+    full = ((counts, 1), (pathlen, 0), (variance, 1), (log, 1))
+    nV = counts.shape[1]
+    if n_chunk >= nV:
+        return launch(0, nV, counts, pathlen, variance, log)
+    for v0 in range(0, nV, n_chunk):
+        v1 = min(nV, v0 + n_chunk)
+        part = [None if t is None else t.new_empty(t.shape[:d] + (v1 - v0,) + t.shape[d + 1:]) for t, d in full]
+        launch(v0, v1, *part)
+        for (t, d), p in zip(full, part):
+            if t is not None:
+                t.narrow(d, v0, v1 - v0).copy_(p)
+
+
 class Projector:
     """Device-resident state of one (scanner, phantom) pair: volume layouts and ray plans.
 
@@ -105,31 +135,18 @@ class Projector:
             # a stacked fan only ever reads its own slices: upload those (one slice of a 512^3 phantom for the
             # reference's single-row scan instead of 128 MiB)
             volume, nz, z_first = volume[z_first:z_first + ct.N_rows], ct.N_rows, 0
-        # ---- the table rows the kernels need.  A uint8 label map may use any of 256 ids (XCAT: input/params.txt:8-9,
-        # plots.py:124) of which many share a composition and some do not occur in the slices scanned: count the ids on
-        # the device, merge ids with the same (density, composition) - their rows of density x mixatten(E) are equal at
-        # every energy - drop the absent ones, and renumber the uploaded copy.  Row 0 stays id 0 (its path length comes
-        # from the chord).  mat_rows[k] = the phantom id whose table row serves compact id k.
         st = stream_ptr()
-        vol_raw = to_dev(volume, torch.uint8, self.dev)
-        cnt = torch.empty(256, dtype=torch.int64, device=self.dev)
-        _native.check(self.lib.dexct_volume_ids(ptr(vol_raw), vol_raw.numel(), ptr(cnt), st), 'dexct_volume_ids')
-        present = cnt.cpu().numpy() > 0
-        if present[phantom.n_materials:].any():
-            raise ValueError('the volume holds a material id without a table entry')
-        self.mat_rows, lut = compact_ids(present, phantom.materials)
-        if any(lut[i] != i for i in np.flatnonzero(present)):
-            _native.check(self.lib.dexct_volume_remap(ptr(vol_raw), vol_raw.numel(), lut.ctypes.data_as(C.POINTER(C.c_uint8)), st),
-                          'dexct_volume_remap')
-        self.id_lut = lut
-        # The 4-rows-per-lane kernels read aligned dwords along z: pad the uploaded copy with empty slices so that
-        # the first imaged slice and the slice count are multiples of 4 (stacked fans only see their own slices,
-        # the in-plane geometry does not change).
-        packed_wanted = kernel in (3, 4, 5, 7, 8) or (kernel == 0 and ct.N_rows >= 64)
+        # ---- 1. the volume on the device, renumbered to compact ids (mat_rows, id_lut, n_mat)
+        vol_raw = self._upload_compact_ids(volume, st)
+        M = self.n_mat
+        # ---- 2. the routes.  A row-parallel kernel (the rows of a (view, channel) pair as lanes) will run on a stacked fan
+        # for kernels 2-5, 7, 8 and for kernel 0 from 64 rows on: it reads the z-fastest layout (vol_zf) and writes the
+        # sinogram row fastest (native_layout 1).  A cone beam has neither (its row kernels read vol_zc, channel fastest).
+        row_parallel = not self.cone and (kernel in (2, 3, 4, 5, 7, 8) or (kernel == 0 and ct.N_rows >= 64))
+        self.native_layout = int(row_parallel)      # 1: [view][channel][row], 0: [view][row][channel]
         # the 2-bit packed volume with bit-sliced counters (rows16_kernel): what kernel 0 picks where it applies
         lanes16 = -(-ct.N_rows // 16)
         group16 = 64 * (-(-lanes16 // 64)) if lanes16 > 32 else (32 if lanes16 > 16 else 16)     # lanes the pair occupies
-        M = self.n_mat = len(self.mat_rows)
         shape2_ok = not self.cone and max(phantom.Nx, phantom.Ny) <= 2047
         # kernel 0 picks it when at least 3/4 of the pair's lane group carry rows (>= 192 rows)
         fills = ct.N_rows >= 192 and 4 * lanes16 >= 3 * group16
@@ -142,20 +159,26 @@ class Projector:
         if kernel == 8 and not self.grouped_packed:
             raise ValueError('kernel 8 (material groups on the 2-bit packed volume) needs a stacked fan, 2..256 materials '
                              'and nx, ny <= 2047')
+        # ---- 3. z padding.  Every row-parallel kernel but kernel 2 (one row per lane, byte loads) reads aligned dwords
+        # along z - the packed volumes 16 slices at a time: pad the uploaded copy with empty slices so that the first
+        # imaged slice and the slice count are multiples of that (stacked fans only see their own slices, the in-plane
+        # geometry does not change).
         align = 16 if (self.use_packed or self.grouped_packed) else 4
-        if not self.cone and packed_wanted and (nz % align or z_first % align):
+        if row_parallel and kernel != 2 and (nz % align or z_first % align):
             lead = (-z_first) % align
             tail = (-(nz + lead)) % align
             vol_raw = torch.nn.functional.pad(vol_raw, (0, 0, 0, 0, lead, tail))      # empty slices (id 0)
             z_first, nz = z_first + lead, nz + lead + tail
+        # ---- 4. geometry and ray plans
         self.geom = _native.FanGeom(ct.N_proj, ct.N_channels, ct.N_rows, z_first, phantom.Nx, phantom.Ny,
                                     nz, 0, phantom.dx, phantom.dy, phantom.dz, ct.SID, ct.SDD)
         self.view_cs = to_dev(ct.view_cs(), torch.float64, self.dev)
         self.chan_cs = to_dev(ct.chan_cs(), torch.float64, self.dev)
-        n_local = self.view_end - self.view_begin
-        self.plan = torch.empty(n_local * ct.N_channels * _native.PLAN_BYTES, dtype=torch.uint8, device=self.dev)
+        self.plan = torch.empty(self.n_local_views * ct.N_channels * _native.PLAN_BYTES, dtype=torch.uint8, device=self.dev)
         _native.check(self.lib.dexct_fan_plan(C.byref(self.geom), ptr(self.view_cs), ptr(self.chan_cs),
                                               self.view_begin, self.view_end, ptr(self.plan), st), 'dexct_fan_plan')
+        # ---- 5. the volume layouts: y-x and x-y for the ray-parallel kernels, z fastest (and its 2-bit packing) for the
+        # row-parallel ones, the cone beam's own
         self.vol_yx = vol_raw.contiguous()
         self.vol_xy = torch.empty_like(self.vol_yx)
         self.vol_zc = None
@@ -169,17 +192,8 @@ class Projector:
             kernel = self.kernel = 1
             self.row_z = to_dev(ct.row_z(), torch.float64, self.dev)
             if self.cone_rows:
-                nb = self.lib.dexct_cone_layout_bytes(phantom.Nx, phantom.Ny, nz)
-                if self.cone_groups:
-                    self.vol_zc = torch.empty(((M + 2) // 3) * nb, dtype=torch.uint8, device=self.dev)
-                    _native.check(self.lib.dexct_cone_layout_groups(ptr(self.vol_yx), phantom.Nx, phantom.Ny, nz, M, ptr(self.vol_zc), st),
-                                  'dexct_cone_layout_groups')
-                else:
-                    self.vol_zc = torch.empty(nb, dtype=torch.uint8, device=self.dev)
-                    _native.check(self.lib.dexct_cone_layout(ptr(self.vol_yx), phantom.Nx, phantom.Ny, nz, ptr(self.vol_zc), st),
-                                  'dexct_cone_layout')
-        want_zf = kernel in (2, 3, 4, 5, 7, 8) or (kernel == 0 and ct.N_rows >= 64)
-        self.vol_zf = torch.empty_like(self.vol_yx) if want_zf else None
+                self._cone_layout(nz, st)
+        self.vol_zf = torch.empty_like(self.vol_yx) if row_parallel else None
         _native.check(self.lib.dexct_volume_layouts(ptr(self.vol_yx), phantom.Nx, phantom.Ny, nz,
                                                     ptr(self.vol_xy), ptr(self.vol_zf), st), 'dexct_volume_layouts')
         self.vol_z2 = None
@@ -187,21 +201,53 @@ class Projector:
             self.vol_z2 = torch.empty(self.vol_zf.numel() // 4, dtype=torch.uint8, device=self.dev)
             _native.check(self.lib.dexct_volume_pack2(ptr(self.vol_zf), self.vol_zf.numel(), ptr(self.vol_z2), st),
                           'dexct_volume_pack2')
+        # ---- 6. group codes of the material-group passes
         aligned = nz % 4 == 0 and z_first % 4 == 0
-        self.grouped = not self.grouped_packed and (kernel == 4 or (kernel == 0 and want_zf and M > 4 and aligned))
+        self.grouped = not self.grouped_packed and (kernel == 4 or (kernel == 0 and row_parallel and M > 4 and aligned))
+        if self.grouped and not (2 <= M <= 256 and aligned):
+            raise ValueError('kernel 4 needs 2..256 materials')
         self.codes = None
-        if self.grouped_packed:
+        if self.grouped_packed or self.grouped:
             n_groups = (M - 1 + 2) // 3
-            self.codes = torch.empty((n_groups, self.vol_zf.numel() // 4), dtype=torch.uint8, device=self.dev)
-            _native.check(self.lib.dexct_volume_groups_pack2(ptr(self.vol_zf), self.vol_zf.numel(), M, ptr(self.codes), st),
-                          'dexct_volume_groups_pack2')
-        elif self.grouped:
-            if not (2 <= M <= 256 and aligned):
-                raise ValueError('kernel 4 needs 2..256 materials')
-            n_groups = (M - 1 + 2) // 3
-            self.codes = torch.empty((n_groups,) + tuple(self.vol_zf.shape), dtype=torch.uint8, device=self.dev)
-            _native.check(self.lib.dexct_volume_groups(ptr(self.vol_zf), self.vol_zf.numel(), M, ptr(self.codes), st),
-                          'dexct_volume_groups')
+            shape, fn = (((self.vol_zf.numel() // 4,), 'dexct_volume_groups_pack2') if self.grouped_packed
+                         else (tuple(self.vol_zf.shape), 'dexct_volume_groups'))
+            self.codes = torch.empty((n_groups,) + shape, dtype=torch.uint8, device=self.dev)
+            _native.check(getattr(self.lib, fn)(ptr(self.vol_zf), self.vol_zf.numel(), M, ptr(self.codes), st), fn)
+        # the material-group passes of either geometry: they go through in view chunks (_in_view_chunks)
+        self._groups = self.cone_groups or self.grouped or self.grouped_packed
+
+    def _upload_compact_ids(self, volume, st):
+        """The volume on the device, renumbered to the table rows the kernels need; sets mat_rows, id_lut and n_mat."""
+        # A uint8 label map may use any of 256 ids (XCAT: input/params.txt:8-9, plots.py:124) of which many share a
+        # composition and some do not occur in the slices scanned: count the ids on the device, merge ids with the same
+        # (density, composition) - their rows of density x mixatten(E) are equal at every energy - drop the absent ones, and
+        # renumber the uploaded copy.  Row 0 stays id 0 (its path length comes from the chord).  mat_rows[k] = the phantom id
+        # whose table row serves compact id k.
+        vol_raw = to_dev(volume, torch.uint8, self.dev)
+        cnt = torch.empty(256, dtype=torch.int64, device=self.dev)
+        _native.check(self.lib.dexct_volume_ids(ptr(vol_raw), vol_raw.numel(), ptr(cnt), st), 'dexct_volume_ids')
+        present = cnt.cpu().numpy() > 0
+        if present[self.phantom.n_materials:].any():
+            raise ValueError('the volume holds a material id without a table entry')
+        self.mat_rows, lut = compact_ids(present, self.phantom.materials)
+        if any(lut[i] != i for i in np.flatnonzero(present)):
+            _native.check(self.lib.dexct_volume_remap(ptr(vol_raw), vol_raw.numel(), lut.ctypes.data_as(C.POINTER(C.c_uint8)), st),
+                          'dexct_volume_remap')
+        self.id_lut, self.n_mat = lut, len(self.mat_rows)
+        return vol_raw
+
+    def _cone_layout(self, nz, st):
+        """vol_zc: what the cone beam's row kernels read - one layout, or one per group of three materials."""
+        ph, M = self.phantom, self.n_mat
+        nb = self.lib.dexct_cone_layout_bytes(ph.Nx, ph.Ny, nz)
+        if self.cone_groups:
+            self.vol_zc = torch.empty(((M + 2) // 3) * nb, dtype=torch.uint8, device=self.dev)
+            _native.check(self.lib.dexct_cone_layout_groups(ptr(self.vol_yx), ph.Nx, ph.Ny, nz, M, ptr(self.vol_zc), st),
+                          'dexct_cone_layout_groups')
+        else:
+            self.vol_zc = torch.empty(nb, dtype=torch.uint8, device=self.dev)
+            _native.check(self.lib.dexct_cone_layout(ptr(self.vol_yx), ph.Nx, ph.Ny, nz, ptr(self.vol_zc), st),
+                          'dexct_cone_layout')
 
     @property
     def n_local_views(self):
@@ -235,12 +281,19 @@ class Projector:
             self._bounds = (l_max, c_max)
         return self._bounds
 
-    def upload_tables(self, specs, quadrature=None):
+    def upload_tables(self, specs, quadrature=None, noise=False):
         """E, mu [n_mat, nE] and w [S, nE] on the device (float32) and the S unattenuated signals.  ``quadrature='reduced'``
         (or DEXCT_QUADRATURE=reduced) swaps the energy grid for the shorter one of quadrature.reduce_tables where it applies
-        (<= 4 table rows, bound verified); ``self.quadrature_info`` then says what was used (None: the full grid)."""
-        E, mu, w = merged_tables(self.ct, self.phantom, specs)
+        (<= 4 table rows, bound verified); ``self.quadrature_info`` then says what was used (None: the full grid).
+        ``noise`` (as Projector.project takes it) appends the [S, nE] device table of its noise model - True / 'gaussian': the
+        variance weights (project_tables' ``w2_d``); 'poisson': the photons per bin, w / (signal per photon) - and keeps the full
+        grid, whose bins the variance and the photon counts are defined on (``quadrature`` plays no part)."""
+        dev32 = lambda x: to_dev(x, torch.float32, self.dev)
+        E, mu, w, w2 = merged_tables(self.ct, self.phantom, specs, with_variance=True)
         mu_c, air = self.compact(mu), w.sum(axis=1)
+        if noise:
+            extra = w / (E if self.ct.eid else np.ones_like(E)) if noise == 'poisson' else w2
+            return E, dev32(mu_c), dev32(w), air, dev32(extra)
         self.quadrature_info = None
         if _want_reduced(quadrature):
             from . import quadrature as _q
@@ -248,14 +301,7 @@ class Projector:
             if red is not None:
                 cols, w, self.quadrature_info = red
                 E, mu_c = E[cols], mu_c[:, cols]
-        return (E, to_dev(mu_c, torch.float32, self.dev), to_dev(w, torch.float32, self.dev), air)
-
-    @property
-    def native_layout(self):
-        """1 (row fastest) when a row-parallel kernel will run, else 0 (channel fastest)."""
-        if self.kernel in (2, 3, 4, 5, 7, 8):
-            return 1
-        return 1 if (self.kernel == 0 and self.vol_zf is not None and self.ct.N_rows >= 64) else 0
+        return E, dev32(mu_c), dev32(w), air
 
     def project_tables(self, mu_d, w_d, want_pathlen=False, out=None, layout=0, w2_d=None, seed=0, air=None,
                        log_out=None, views=None, want_variance=False):
@@ -277,150 +323,47 @@ class Projector:
         ``want_variance``: the variance of the detected signal as a further result (appended last; tests).
         ``views=(a, b)``: only the local views [a, b) of this projector's range (outputs sized for b - a views): a step that
         hands its sinogram on in chunks projects chunk by chunk (bench.py, the sharded step)."""
-        # the kernels read the tables through raw pointers: dense float32, whatever view the caller built
-        # (torch.tensor(w[:, keep]) keeps NumPy's column-major result of the advanced index)
-        mu_d, w_d = (t.to(dtype=torch.float32).contiguous() for t in (mu_d, w_d))
-        w2_d = None if w2_d is None else w2_d.to(dtype=torch.float32).contiguous()
+        # ---- 1. the tables and the view range
+        mu_d, w_d, w2_d, sl0, sl1 = self._check_tables(mu_d, w_d, w2_d, views)
         S, nE = w_d.shape
-        if mu_d.shape[1] != nE or (w2_d is not None and tuple(w2_d.shape) != (S, nE)):
-            raise ValueError(f'tables disagree: mu {tuple(mu_d.shape)}, w {tuple(w_d.shape)}' + ('' if w2_d is None else f', w2 {tuple(w2_d.shape)}'))
-        sl0, sl1 = (0, self.n_local_views) if views is None else (int(views[0]), int(views[1]))
-        if not 0 <= sl0 < sl1 <= self.n_local_views:
-            raise ValueError(f'views={views}: a non-empty range within the {self.n_local_views} local views')
-        plan_ptr = self.plan.data_ptr() + sl0 * self.ct.N_channels * _native.PLAN_BYTES
-        vb, ve = self.view_begin + sl0, self.view_begin + sl1
-        if mu_d.shape[0] != self.n_mat:
-            if mu_d.shape[0] != self.phantom.n_materials:
-                raise ValueError(f'mu has {mu_d.shape[0]} rows; expected {self.n_mat} (compact ids, Projector.compact) or '
-                                 f'{self.phantom.n_materials} (one per phantom id)')
-            mu_d = mu_d[torch.as_tensor(self.mat_rows, device=mu_d.device)].contiguous()
-        M = self.n_mat
-        ct = self.ct
-        nV, nR, nC = sl1 - sl0, ct.N_rows, ct.N_channels
+        M, nV, nR, nC = self.n_mat, sl1 - sl0, self.ct.N_rows, self.ct.N_channels
+        # ---- 2. outputs and layouts: the kernel writes ``run_layout``; where that is not the layout wanted, a transpose follows
+        new = lambda shape: torch.empty(shape, dtype=torch.float32, device=self.dev)
         native = self.native_layout
         want = native if layout is None else layout
         shape = {0: (S, nV, nR, nC), 1: (S, nV, nC, nR)}
         direct = want == native or nR == 1
         run_layout = want if direct else native
-        if out is not None and direct:
-            counts = out
-        else:
-            counts = torch.empty(shape[run_layout], dtype=torch.float32, device=self.dev)
-        pathlen = None
-        if want_pathlen:
-            pl_shape = (nV, nR, nC, M) if run_layout == 0 else (nV, nC, nR, M)
-            pathlen = torch.empty(pl_shape, dtype=torch.float32, device=self.dev)
-        noisy = w2_d is not None
-        # kernels that draw the noise sample themselves (ABI 6): the packed stacked fan, the cone beam, and the detection pass of
-        # the material groups (<= 2 spectra, <= 48 table rows); everything else writes the variance for dexct_add_noise
-        groups = self.cone_groups or (not self.cone and (self.grouped_packed or self.grouped))
-        in_kernel = noisy and ((self.cone and not self.cone_groups) or (self.use_packed and S <= 2 and not groups)
-                               or (groups and S <= 2 and M <= 48))
-        variance = torch.empty_like(counts) if (noisy and (want_variance or not in_kernel)) else None
-        nz = _native.noise(seed) if in_kernel else None
         # the log sinogram: written by the detection store when the kernel's layout is the one wanted; else together with the
         # transpose at the end (dexct_transpose_log: the counts are read once for both outputs)
         fuse_log = air is not None and not direct
+        counts = out if (out is not None and direct) else new(shape[run_layout])
+        pathlen = new((nV, nR, nC, M) if run_layout == 0 else (nV, nC, nR, M)) if want_pathlen else None
+        # ---- 3. who draws the noise: the kernel in its detection, or dexct_add_noise from the variance the kernel writes
+        noisy = w2_d is not None
+        in_kernel = noisy and self._samples_in_kernel(S)
+        variance = torch.empty_like(counts) if (noisy and (want_variance or not in_kernel)) else None
         log = None
         if air is not None and not fuse_log:
-            log = log_out if log_out is not None else torch.empty(shape[run_layout], dtype=torch.float32, device=self.dev)
-        # fused into the detection store, except where the noisy counts only exist after dexct_add_noise
-        lo = _native.log_out(ptr(log), air) if (log is not None and (not noisy or in_kernel)) else None
-        if self.cone:
-            max_dz = float(np.max(np.abs(self.ct.row_z() - self.ct.src_z)))
-
-            # (quantum noise: the variance of the detected signal comes out of the same launch and the kernel draws the sample -
-            # round 5 ran the kernel a second time with w2 as weights)
-            if self.cone_groups:
-                # more than 3 table rows: one traversal per group of three materials into M planes of path lengths, one detection
-                # pass over them; many materials on a large scan go through in view chunks (the scratch stays bounded)
-                per_view = M * nR * nC * 4
-                n_chunk = max(1, min(nV, _GROUP_SCRATCH_BYTES // max(per_view, 1)))
-                scratch = torch.empty((M, n_chunk * nR * nC), dtype=torch.float32, device=self.dev)
-                for v0 in range(0, nV, n_chunk):
-                    v1 = min(nV, v0 + n_chunk)
-                    whole = v0 == 0 and v1 == nV
-                    c_t = counts if whole else torch.empty((S, v1 - v0, nR, nC), dtype=torch.float32, device=self.dev)
-                    p_t = pathlen if (whole or pathlen is None) else torch.empty((v1 - v0, nR, nC, M), dtype=torch.float32, device=self.dev)
-                    v_t = variance if (whole or variance is None) else torch.empty_like(c_t)
-                    l_t = log if (whole or lo is None) else torch.empty_like(c_t)
-                    lo_t = lo if whole else (_native.log_out(ptr(l_t), air) if lo is not None else None)
-                    _native.check(self.lib.dexct_cone_project_grouped(
-                        C.byref(self.geom), plan_ptr + v0 * nC * _native.PLAN_BYTES, ptr(self.view_cs), ptr(self.chan_cs), ptr(self.row_z),
-                        self.ct.src_z, max_dz, vb + v0, vb + v1, ptr(self.vol_zc), M, nE, S, ptr(mu_d), ptr(w_d), ptr(c_t), ptr(p_t),
-                        ptr(scratch), lo_t, ptr(w2_d), ptr(v_t), nz, stream_ptr()), 'dexct_cone_project_grouped')
-                    if not whole:
-                        counts[:, v0:v1].copy_(c_t)
-                        if pathlen is not None:
-                            pathlen[v0:v1].copy_(p_t)
-                        if variance is not None:
-                            variance[:, v0:v1].copy_(v_t)
-                        if lo is not None:
-                            log[:, v0:v1].copy_(l_t)
-            elif self.cone_rows:
-                _native.check(self.lib.dexct_cone_project_rows(
-                    C.byref(self.geom), plan_ptr, ptr(self.view_cs), ptr(self.chan_cs), ptr(self.row_z),
-                    self.ct.src_z, max_dz, vb, ve, ptr(self.vol_zc), M, nE, S, ptr(mu_d),
-                    ptr(w_d), ptr(counts), ptr(pathlen), lo, ptr(w2_d), ptr(variance), nz, stream_ptr()), 'dexct_cone_project_rows')
-            else:
-                _native.check(self.lib.dexct_cone_project(
-                    C.byref(self.geom), plan_ptr, ptr(self.view_cs), ptr(self.chan_cs), ptr(self.row_z),
-                    self.ct.src_z, max_dz, vb, ve, ptr(self.vol_yx), ptr(self.vol_xy), M, nE, S,
-                    ptr(mu_d), ptr(w_d), ptr(counts), ptr(pathlen), lo, ptr(w2_d), ptr(variance), nz, stream_ptr()), 'dexct_cone_project')
-        elif self.use_packed and (not noisy or in_kernel):      # (noise on > 2 spectra: the byte-volume kernel below)
-            _native.check(self.lib.dexct_siddon_project_packed(
-                C.byref(self.geom), plan_ptr, vb, ve, ptr(self.vol_z2), M, nE, S,
-                ptr(mu_d), ptr(w_d), ptr(counts), ptr(pathlen), run_layout, lo, ptr(w2_d), ptr(variance), nz, stream_ptr()),
-                'dexct_siddon_project_packed')
-        elif self.grouped_packed or self.grouped:        # noise too: the detection pass carries the variance
-            fn, what = ((self.lib.dexct_siddon_project_grouped_packed, 'dexct_siddon_project_grouped_packed') if self.grouped_packed
-                        else (self.lib.dexct_siddon_project_grouped, 'dexct_siddon_project_grouped'))
-            # the per-material accumulators of the group passes: M x rays floats.  Many materials on a large scan go through
-            # in view chunks so that this scratch stays below _GROUP_SCRATCH_BYTES (the outputs of a chunk are copied into place)
-            per_view = M * nR * nC * 4
-            n_chunk = max(1, min(nV, _GROUP_SCRATCH_BYTES // max(per_view, 1)))
-            if n_chunk >= nV:
-                scratch = torch.empty((M, nV * nR * nC), dtype=torch.float32, device=self.dev)
-                _native.check(fn(C.byref(self.geom), plan_ptr, vb, ve, ptr(self.codes), M, nE, S,
-                                 ptr(mu_d), ptr(w_d), ptr(counts), ptr(pathlen), ptr(scratch), run_layout, ptr(w2_d), ptr(variance),
-                                 lo, nz, stream_ptr()), what)
-            else:
-                scratch = torch.empty((M, n_chunk * nR * nC), dtype=torch.float32, device=self.dev)
-                for v0 in range(0, nV, n_chunk):
-                    v1 = min(nV, v0 + n_chunk)
-                    sub = (S, v1 - v0) + tuple(counts.shape[2:])
-                    c_t = torch.empty(sub, dtype=torch.float32, device=self.dev)
-                    p_t = torch.empty((v1 - v0,) + tuple(pathlen.shape[1:]), dtype=torch.float32, device=self.dev) if pathlen is not None else None
-                    v_t = torch.empty_like(c_t) if variance is not None else None
-                    l_t = torch.empty_like(c_t) if lo is not None else None
-                    lo_t = _native.log_out(ptr(l_t), air) if lo is not None else None
-                    _native.check(fn(C.byref(self.geom), plan_ptr + v0 * nC * _native.PLAN_BYTES, vb + v0,
-                                     vb + v1, ptr(self.codes), M, nE, S, ptr(mu_d), ptr(w_d), ptr(c_t), ptr(p_t),
-                                     ptr(scratch), run_layout, ptr(w2_d), ptr(v_t), lo_t, nz, stream_ptr()), what)
-                    counts[:, v0:v1].copy_(c_t)
-                    if pathlen is not None:
-                        pathlen[v0:v1].copy_(p_t)
-                    if variance is not None:
-                        variance[:, v0:v1].copy_(v_t)
-                    if l_t is not None:
-                        log[:, v0:v1].copy_(l_t)
-        else:
-            _native.check(self.lib.dexct_siddon_project(
-                C.byref(self.geom), plan_ptr, vb, ve, ptr(self.vol_yx),
-                ptr(self.vol_xy), ptr(self.vol_zf), M, nE, S, ptr(mu_d), ptr(w_d), ptr(counts), ptr(pathlen),
-                3 if self.kernel in (7, 8) else self.kernel, run_layout, ptr(w2_d), ptr(variance), lo, stream_ptr()),
-                'dexct_siddon_project')
+            log = log_out if log_out is not None else new(shape[run_layout])
+        # ---- 4. the launch.  The log is fused into the detection store, except where the noisy counts only exist after
+        # dexct_add_noise
+        call = _Call(plan_ptr=self.plan.data_ptr() + sl0 * nC * _native.PLAN_BYTES, vb=self.view_begin + sl0, S=S, nE=nE,
+                     mu=ptr(mu_d), w=ptr(w_d), w2=ptr(w2_d), air=air, nz=_native.noise(seed) if in_kernel else None,
+                     run_layout=run_layout, packed=self.use_packed and (not noisy or in_kernel))
+        self._launch(call, counts, pathlen, variance, log if (not noisy or in_kernel) else None)
+        # ---- 5. the post passes
         if noisy and not in_kernel:
             _native.check(self.lib.dexct_add_noise(ptr(counts), ptr(variance), S, nV, nR, nC, run_layout,
-                                                   vb, int(seed) & (2 ** 64 - 1), stream_ptr()),
+                                                   call.vb, int(seed) & (2 ** 64 - 1), stream_ptr()),
                           'dexct_add_noise')
             if log is not None:
                 self.sino_log(counts, air, log)
         if not direct:
-            dst = out if out is not None else torch.empty(shape[want], dtype=torch.float32, device=self.dev)
+            dst = out if out is not None else new(shape[want])
             r, c = (nC, nR) if run_layout == 1 else (nR, nC)
             if fuse_log:
-                log = log_out if log_out is not None else torch.empty(shape[want], dtype=torch.float32, device=self.dev)
+                log = log_out if log_out is not None else new(shape[want])
             self.transpose_log(counts, dst, log, air, r, c)
             counts = dst
             if pathlen is not None:
@@ -434,22 +377,111 @@ class Projector:
             res = res + (variance,)
         return res if len(res) > 1 else res[0]
 
+    def _check_tables(self, mu_d, w_d, w2_d, views):
+        """project_tables' tables as the kernels read them, mu with the rows of the compact ids, and the local view range."""
+        # the kernels read the tables through raw pointers: dense float32, whatever view the caller built
+        # (torch.tensor(w[:, keep]) keeps NumPy's column-major result of the advanced index)
+        mu_d, w_d = (t.to(dtype=torch.float32).contiguous() for t in (mu_d, w_d))
+        w2_d = None if w2_d is None else w2_d.to(dtype=torch.float32).contiguous()
+        S, nE = w_d.shape
+        if mu_d.shape[1] != nE or (w2_d is not None and tuple(w2_d.shape) != (S, nE)):
+            raise ValueError(f'tables disagree: mu {tuple(mu_d.shape)}, w {tuple(w_d.shape)}' + ('' if w2_d is None else f', w2 {tuple(w2_d.shape)}'))
+        sl0, sl1 = (0, self.n_local_views) if views is None else (int(views[0]), int(views[1]))
+        if not 0 <= sl0 < sl1 <= self.n_local_views:
+            raise ValueError(f'views={views}: a non-empty range within the {self.n_local_views} local views')
+        if mu_d.shape[0] != self.n_mat:
+            if mu_d.shape[0] != self.phantom.n_materials:
+                raise ValueError(f'mu has {mu_d.shape[0]} rows; expected {self.n_mat} (compact ids, Projector.compact) or '
+                                 f'{self.phantom.n_materials} (one per phantom id)')
+            mu_d = mu_d[torch.as_tensor(self.mat_rows, device=mu_d.device)].contiguous()
+        return mu_d, w_d, w2_d, sl0, sl1
+
+    def _samples_in_kernel(self, S):
+        """Whether the kernel that will run draws the noise sample of ``S`` spectra itself (ABI 6: struct dexct_noise), in its
+        detection; otherwise it writes the variance and dexct_add_noise draws the same sample from it.  The host-side mirror
+        of proj::noise_log_args (csrc/proj_host.h), which refuses a sample where this says no: the detection pass of the
+        material groups and the packed stacked fan hold two spectra, the group pass up to _NOISE_MAX_GROUP_ROWS table rows;
+        the cone beam without groups always samples; the byte-volume stacked fan never does."""
+        if self._groups:
+            return S <= _NOISE_MAX_SPECTRA and self.n_mat <= _NOISE_MAX_GROUP_ROWS
+        return self.cone or (self.use_packed and S <= _NOISE_MAX_SPECTRA)
+
+    def _launch(self, c, counts, pathlen, variance, log):
+        """The projection launch of one project_tables call ``c`` (_Call) on the route __init__ settled: one library call, or
+        one per view chunk for the material groups.  ``log``: where the detection store writes the log sinogram (None: it
+        writes none)."""
+        if self._groups:
+            # one traversal per group of three materials into M planes of path lengths (the scratch), one detection pass
+            # over them
+            n_chunk, scratch = self._group_scratch(counts.shape[1])
+            return _in_view_chunks(lambda *chunk: self._launch_groups(c, scratch, *chunk), n_chunk, counts, pathlen, variance, log)
+        lib, geom, M, ve = self.lib, C.byref(self.geom), self.n_mat, c.vb + counts.shape[1]
+        lo = _native.log_out(ptr(log), c.air)
+        if self.cone and self.cone_rows:
+            # (quantum noise: the variance of the detected signal comes out of the same launch and the kernel draws the sample)
+            _native.check(lib.dexct_cone_project_rows(
+                geom, c.plan_ptr, *self._cone_rays(), c.vb, ve, ptr(self.vol_zc), M, c.nE, c.S, c.mu, c.w, ptr(counts),
+                ptr(pathlen), lo, c.w2, ptr(variance), c.nz, stream_ptr()), 'dexct_cone_project_rows')
+        elif self.cone:
+            _native.check(lib.dexct_cone_project(
+                geom, c.plan_ptr, *self._cone_rays(), c.vb, ve, ptr(self.vol_yx), ptr(self.vol_xy), M, c.nE, c.S, c.mu, c.w,
+                ptr(counts), ptr(pathlen), lo, c.w2, ptr(variance), c.nz, stream_ptr()), 'dexct_cone_project')
+        elif c.packed:                                          # (noise on > 2 spectra: the byte-volume kernel below)
+            _native.check(lib.dexct_siddon_project_packed(
+                geom, c.plan_ptr, c.vb, ve, ptr(self.vol_z2), M, c.nE, c.S, c.mu, c.w, ptr(counts), ptr(pathlen), c.run_layout, lo,
+                c.w2, ptr(variance), c.nz, stream_ptr()), 'dexct_siddon_project_packed')
+        else:
+            _native.check(lib.dexct_siddon_project(
+                geom, c.plan_ptr, c.vb, ve, ptr(self.vol_yx), ptr(self.vol_xy), ptr(self.vol_zf), M, c.nE, c.S, c.mu, c.w,
+                ptr(counts), ptr(pathlen), 3 if self.kernel in (7, 8) else self.kernel, c.run_layout, c.w2, ptr(variance), lo,
+                stream_ptr()), 'dexct_siddon_project')
+
+    def _cone_rays(self):
+        """What every cone entry point takes after the plan: the view and channel directions, the rows' heights, the
+        source's height and the largest |row height - source height|."""
+        max_dz = float(np.max(np.abs(self.ct.row_z() - self.ct.src_z)))
+        return ptr(self.view_cs), ptr(self.chan_cs), ptr(self.row_z), self.ct.src_z, max_dz
+
+    def _group_scratch(self, nV):
+        """The per-material accumulators of the group passes: M x rays floats.  Many materials on a large scan go through in
+        view chunks so that this scratch stays below _GROUP_SCRATCH_BYTES.  Returns (views per chunk, scratch)."""
+        rays = self.ct.N_rows * self.ct.N_channels
+        n_chunk = max(1, min(nV, _GROUP_SCRATCH_BYTES // (self.n_mat * rays * 4)))
+        return n_chunk, torch.empty((self.n_mat, n_chunk * rays), dtype=torch.float32, device=self.dev)
+
+    def _launch_groups(self, c, scratch, v0, v1, counts, pathlen, variance, log):
+        """The material-group passes over the views [v0, v1) of call ``c`` into outputs of that many views.  (The cone and the
+        fan entry points order scratch / run_layout / log_out / weights2 / variance / noise differently.)"""
+        geom, M, lo = C.byref(self.geom), self.n_mat, _native.log_out(ptr(log), c.air)
+        plan_ptr = c.plan_ptr + v0 * self.ct.N_channels * _native.PLAN_BYTES
+        if self.cone:
+            _native.check(self.lib.dexct_cone_project_grouped(
+                geom, plan_ptr, *self._cone_rays(), c.vb + v0, c.vb + v1, ptr(self.vol_zc), M, c.nE, c.S, c.mu, c.w, ptr(counts),
+                ptr(pathlen), ptr(scratch), lo, c.w2, ptr(variance), c.nz, stream_ptr()), 'dexct_cone_project_grouped')
+        else:
+            what = 'dexct_siddon_project_grouped_packed' if self.grouped_packed else 'dexct_siddon_project_grouped'
+            _native.check(getattr(self.lib, what)(
+                geom, plan_ptr, c.vb + v0, c.vb + v1, ptr(self.codes), M, c.nE, c.S, c.mu, c.w, ptr(counts), ptr(pathlen),
+                ptr(scratch), c.run_layout, c.w2, ptr(variance), lo, c.nz, stream_ptr()), what)
+
+    @staticmethod
+    def _air_array(air, S):
+        """The S unattenuated signals as the float array the log passes take."""
+        return (C.c_float * S)(*[float(x) for x in air[:S]])
+
     def transpose_log(self, src, dst, log_dst, air, rows, cols):
         """src [S, n, rows, cols] -> dst [S, n, cols, rows] and (``log_dst`` not None) ln(air[s] / dst[s]) in the same pass
         (dexct_transpose_log)."""
-        import ctypes as _C
         S, n = int(src.shape[0]), int(src.shape[1])
-        arr = (_C.c_float * S)(*[float(x) for x in air[:S]]) if log_dst is not None else None
+        arr = self._air_array(air, S) if log_dst is not None else None
         _native.check(self.lib.dexct_transpose_log(ptr(src), ptr(dst), ptr(log_dst), arr, S, n, rows, cols, stream_ptr()),
                       'dexct_transpose_log')
 
     def sino_log(self, counts, air, out=None):
         """ln(air[s] / counts[s]) as a pass of its own (dexct_sino_log): noisy and gathered sinograms."""
-        import ctypes as _C
         S = counts.shape[0]
         out = torch.empty_like(counts) if out is None else out
-        arr = (_C.c_float * S)(*[float(x) for x in air[:S]])
-        _native.check(self.lib.dexct_sino_log(ptr(counts), arr, S, counts[0].numel(), ptr(out), stream_ptr()),
+        _native.check(self.lib.dexct_sino_log(ptr(counts), self._air_array(air, S), S, counts[0].numel(), ptr(out), stream_ptr()),
                       'dexct_sino_log')
         return out
 
@@ -468,17 +500,13 @@ class Projector:
                 res = (res if isinstance(res, tuple) else (res,))
                 res = res + (self.sino_log(res[0], air),)
             return res, air
-        _, mu, w, w2 = merged_tables(self.ct, self.phantom, specs, with_variance=True)
-        mu_d, w_d, w2_d = (to_dev(x, torch.float32, self.dev) for x in (self.compact(mu), w, w2))
-        air = w.sum(axis=1)
+        _, mu_d, w_d, air, w2_d = self.upload_tables(specs, noise=True)
         return self.project_tables(mu_d, w_d, want_pathlen, layout=layout, w2_d=w2_d, seed=seed,
                                    air=air if want_log else None), air
 
     def _project_poisson(self, specs, want_pathlen, layout, seed):
-        E, mu, w = merged_tables(self.ct, self.phantom, specs)
-        gain = E if self.ct.eid else np.ones_like(E)
-        mu_d, w_d = to_dev(self.compact(mu), torch.float32, self.dev), to_dev(w, torch.float32, self.dev)
-        ph_d, gain_d = to_dev(w / gain, torch.float32, self.dev), to_dev(gain, torch.float32, self.dev)
+        E, mu_d, w_d, air, ph_d = self.upload_tables(specs, noise='poisson')
+        gain_d = to_dev(E if self.ct.eid else np.ones_like(E), torch.float32, self.dev)
         # path lengths from whichever traversal kernel applies (its noise-free counts are discarded)
         want = self.native_layout if layout is None else layout
         counts, pathlen = self.project_tables(mu_d, w_d, want_pathlen=True, layout=want)
@@ -487,7 +515,7 @@ class Projector:
         _native.check(self.lib.dexct_poisson_detect(
             ptr(pathlen), ptr(mu_d), ptr(ph_d), ptr(gain_d), mu_d.shape[0], nE, S, nV, nR, nC, want, self.view_begin,
             int(seed) & (2 ** 64 - 1), ptr(counts), stream_ptr()), 'dexct_poisson_detect')
-        return ((counts, pathlen) if want_pathlen else counts), w.sum(axis=1)
+        return ((counts, pathlen) if want_pathlen else counts), air
 
     def trace(self, rays_vrc, max_seg=None):
         """Voxel-index sequence and float32 piece lengths of selected rays (views relative to the shard)."""
@@ -532,8 +560,7 @@ verify_volume = True
 
 
 def _verify_enabled():
-    import os
-    return verify_volume and os.environ.get('DEXCT_VERIFY_VOLUME', '1') != '0'
+    return verify_volume and _os.environ.get('DEXCT_VERIFY_VOLUME', '1') != '0'
 
 
 def _hash64(a):
@@ -600,6 +627,28 @@ def _projector(ct, phantom, view_range):
     return pj, bool(_verify_enabled() and pj.volume_hash is not None)
 
 
+def _stale(pj, check, phantom):
+    """Whether ``phantom.volume`` is no longer the bytes the cached state ``pj`` was built from (``check``: _projector asks
+    for the comparison).  Called between queueing the GPU work and waiting for it: the checksum costs the call no time."""
+    return check and _hash64(phantom.volume) != pj.volume_hash
+
+
+def _checked(out, stale, ct, phantom, specs, noise, seed, quadrature):
+    """The tail of get_sinos: ``out``, the per-spectrum (raw, log) pairs [N_proj, N_rows, N_channels] that the caller holds
+    through this list alone, with the single row squeezed - or, if they are ``stale``, the projection done again."""
+    if stale:
+        # phantom.volume was edited in place since the device state was built (no touch()): what was just computed is of
+        # the old bytes.  Release it, rebuild from the current bytes and project again - the result is what the reference,
+        # which builds its state on every call, returns.  (Under torch.distributed every rank holds the same phantom and
+        # takes the same branch.)
+        out.clear()
+        invalidate()
+        return get_sinos(ct, phantom, specs, noise=noise, seed=seed, quadrature=quadrature)
+    if ct.N_rows == 1:
+        return [(r[:, 0, :], l[:, 0, :]) for r, l in out]
+    return out
+
+
 _SINO_CHUNKS = 8                # view chunks of a large noise-free projection on one process: chunk k + 1 is projected while chunk k
                                 # crosses PCIe (3.3 GB of results take 58 ms, their kernels 12)
 
@@ -610,13 +659,7 @@ def _get_sinos_pipelined(pj, check, ct, phantom, specs, seed, quadrature, noise=
     kernels on the same rays as the single launch: the same bits - with quantum noise too (``noise`` True: the Philox counter is
     the global view).  One host block per spectrum and output (_device.LazyPinnedResult: touched and locked chunk by chunk in
     front of the copies, unlocked before it is returned)."""
-    w2_d = None
-    if noise:
-        _, mu, w, w2 = merged_tables(ct, phantom, specs, with_variance=True)
-        mu_d, w_d, w2_d = (to_dev(x, torch.float32, pj.dev) for x in (pj.compact(mu), w, w2))
-        air = w.sum(axis=1)
-    else:
-        _, mu_d, w_d, air = pj.upload_tables(specs, quadrature)
+    _, mu_d, w_d, air, w2_d = pj.upload_tables(specs, noise=True) if noise else pj.upload_tables(specs, quadrature) + (None,)
     S, nV, nR, nC = len(specs), pj.n_local_views, ct.N_rows, ct.N_channels
     bounds = [_shard.split(nV, k, _SINO_CHUNKS) for k in range(_SINO_CHUNKS)]
     row = nR * nC * 4
@@ -635,17 +678,11 @@ def _get_sinos_pipelined(pj, check, ct, phantom, specs, seed, quadrature, noise=
             for s_i in range(S):
                 holders[s_i][0].download(k, c_k[s_i].data_ptr(), down)
                 holders[s_i][1].download(k, l_k[s_i].data_ptr(), down)
-    stale = check and _hash64(phantom.volume) != pj.volume_hash        # (computed while the GPU works, as in get_sinos)
+    stale = _stale(pj, check, phantom)        # (computed while the GPU works, as in get_sinos)
     down.synchronize()
     out = [(h[0].finish(), h[1].finish()) for h in holders]
     del keep
-    if stale:
-        del out
-        invalidate()
-        return get_sinos(ct, phantom, specs, noise=noise, seed=seed, quadrature=quadrature)
-    if nR == 1:
-        out = [(r[:, 0, :], l[:, 0, :]) for r, l in out]
-    return out
+    return _checked(out, stale, ct, phantom, specs, noise, seed, quadrature)
 
 
 _DOWNLOAD_PIECE = 128 << 20     # bytes of a large result per copy (and per step of the page-locking in front of it)
@@ -691,7 +728,7 @@ def get_sinos(ct, phantom, specs, noise=False, seed=0, quadrature=None):
         for k in range(len(cuts) - 1):
             for holder, t in zip(lz, (counts, log)):
                 holder.download(k, t.data_ptr() + cuts[k], cur)
-        stale = check and _hash64(phantom.volume) != pj.volume_hash
+        stale = _stale(pj, check, phantom)
         cur.synchronize()
         raw, lg = lz[0].finish(), lz[1].finish()
         h_raw = h_lg = None
@@ -699,20 +736,12 @@ def get_sinos(ct, phantom, specs, noise=False, seed=0, quadrature=None):
         h_raw, h_lg = pinned_empty(counts.shape, counts.dtype), pinned_empty(log.shape, log.dtype)
         h_raw.copy_(counts, non_blocking=True)
         h_lg.copy_(log, non_blocking=True)
-        stale = check and _hash64(phantom.volume) != pj.volume_hash
+        stale = _stale(pj, check, phantom)
         torch.cuda.current_stream().synchronize()
         raw, lg = h_raw.numpy(), h_lg.numpy()
-    if stale:
-        # phantom.volume was edited in place since the device state was built (no touch()): what was just computed is of
-        # the old bytes.  Rebuild from the current ones and project again - the result is what the reference, which
-        # builds its state on every call, returns.  (Under torch.distributed every rank holds the same phantom and
-        # takes the same branch.)
-        del raw, lg, h_raw, h_lg, counts, log, res
-        invalidate()
-        return get_sinos(ct, phantom, specs, noise=noise, seed=seed, quadrature=quadrature)
-    if ct.N_rows == 1:
-        raw, lg = raw[:, :, 0, :], lg[:, :, 0, :]
-    return [(raw[k], lg[k]) for k in range(len(specs))]
+    out = [(raw[k], lg[k]) for k in range(len(specs))]
+    del raw, lg, h_raw, h_lg, counts, log, res          # (``out`` alone holds the results: _checked can release them)
+    return _checked(out, stale, ct, phantom, specs, noise, seed, quadrature)
 
 
 def get_sino(ct, phantom, spec, noise=False, seed=0, quadrature=None):
