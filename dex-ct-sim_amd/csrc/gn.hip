@@ -1613,12 +1613,50 @@ __device__ __forceinline__ double nanmax(double m, double v) {
   return (v != v || m != m) ? __builtin_nan("") : fmax(m, v);
 }
 
+// One thread's share of the maximum, at memory speed: 16-byte loads, four of them in flight, the maximum taken in the
+// input's own type (v_max ignores a NaN operand) with "saw a NaN" kept beside it, one conversion to double at the end.
+// The elements before the first 16-byte boundary and after the last whole vector (at most 3 floats or 1 double each) go
+// one by one: callers pass any pointer and length.
+template <typename T>
+__device__ __forceinline__ double thread_max(const T* __restrict__ g, int64_t n) {
+  constexpr int kPer = 16 / (int)sizeof(T);               // elements per load
+  typedef T Vec __attribute__((ext_vector_type(kPer)));
+  T m = -__builtin_huge_val();
+  bool nan = false;
+  auto take = [&](T v) {
+    nan |= v != v;
+    m = fmax(m, v);
+  };
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
+  int64_t head = (int64_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(g) & 15u)) & 15u) / (int64_t)sizeof(T);
+  if (head > n) head = n;
+  const int64_t n_vec = (n - head) / kPer;
+  const Vec* __restrict__ gv = reinterpret_cast<const Vec*>(g + head);
+  int64_t i = tid;
+  for (; i + 3 * stride < n_vec; i += 4 * stride) {
+    Vec v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = gv[i + q * stride];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int e = 0; e < kPer; ++e) take(v[q][e]);
+  }
+  for (; i < n_vec; i += stride) {
+    const Vec v = gv[i];
+#pragma unroll
+    for (int e = 0; e < kPer; ++e) take(v[e]);
+  }
+  // head and tail: fewer than 2 kPer elements in all
+  const int64_t n_edge = n - n_vec * kPer;
+  if (tid < n_edge) take(g[tid < head ? tid : n_vec * kPer + tid]);
+  return nan ? (double)__builtin_nan("") : (double)m;
+}
+
 __global__ __launch_bounds__(256) void max_kernel(const void* __restrict__ g1, int g_is_f64, int64_t n_pix,
                                                   double* __restrict__ out) {
   __shared__ double part[4];
-  double m = -__builtin_huge_val();
-  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n_pix; p += (int64_t)gridDim.x * 256)
-    m = nanmax(m, load_g<double>(g1, g_is_f64, p));
+  double m = g_is_f64 ? thread_max(static_cast<const double*>(g1), n_pix) : thread_max(static_cast<const float*>(g1), n_pix);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = nanmax(m, __shfl_down(m, o, 64));
   if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = m;

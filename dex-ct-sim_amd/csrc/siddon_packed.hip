@@ -7,13 +7,14 @@
 //
 // Counting.  The loaded word x IS 32 one-bit flags: bit 2r = "row r sees id 1", bit 2r + 1 = "row r sees id 2" (ids
 // 0, 1, 2).  n_1 and n_2 per row are therefore per-bit-position population counts over the slabs of the ray.  They are
-// kept BIT-SLICED (Harley-Seal): words ones / twos / fours hold bits 0..2 of the 32 counters, hi[0..7] bits 3..10; eight
-// (Id 3 sets both flags: with 4 ids - a full material group, or a 4-material phantom - a second set of counters runs
-// on x & (x >> 1), the "both" flags at the even positions, and n_1 = n(bit 0) - n_3, n_2 = n(bit 1) - n_3.)  Eight
-// loaded words are folded by seven carry-save adders (3 logic instructions each: a ^ b, (a ^ b) ^ c, majority by bit
-// select); two of the resulting weight-8 words meet in an eighth adder and the carry ripples into hi[] once per 16
-// words: 30 instructions per 8 dwords = 0.23 per row and slab against 0.75 (+ a v_readfirstlane per 4 rows) in
-// rows4_kernel.  The counters are un-sliced once per ray plane.
+// kept BIT-SLICED (Harley-Seal, sliced_count.h): words ones / twos / fours / eights hold bits 0..3 of the 32 counters,
+// hi[0..6] bits 4..10.  (Id 3 sets both flags: with 4 ids - a full material group, or a 4-material phantom - a second
+// set of counters runs on x & (x >> 1), the "both" flags at the even positions, and n_1 = n(bit 0) - n_3,
+// n_2 = n(bit 1) - n_3.)  Sixteen loaded words are folded by fifteen carry-save adders (2 instructions each:
+// v_bitop3_b32 for the majority and for the parity) and the one carry of weight 16 ripples into hi[] (10, two planes
+// per step): 40 instructions per 16 dwords = 0.16 per row and slab against 0.75 (+ a v_readfirstlane per 4 rows) in
+// rows4_kernel.  The crossing slabs go eight at a time (seven adders, a half adder, the ripple: 26 per 8).  The
+// counters are un-sliced once per ray plane.
 // Corrections (float32, in slab order, only where a crossing separates two materials) are applied per row exactly as
 // in rows4_kernel, so per-material path lengths are bit-identical to every other kernel and to the oracle.
 //
@@ -23,95 +24,15 @@
 #include "common.h"
 #include "noise_sample.h"
 #include "proj_host.h"
+#include "sliced_count.h"
 
 namespace dexct {
 
 constexpr int kP16Super = 128;      // slabs staged per pass
 constexpr uint32_t kOob = 0xF0000000u;   // a list offset outside every buffer (< 3.75 GiB): the load returns 0 (air), no traffic
-
-// carry-save adder on 32 one-bit lanes: (h, l) = a + b + c
-__device__ __forceinline__ void csa(uint32_t& h, uint32_t& l, uint32_t a, uint32_t b, uint32_t c) {
-  const uint32_t u = a ^ b;
-  h = (a & b) | (u & c);
-  l = u ^ c;
-}
-
-struct Sliced {
-  uint32_t ones = 0, twos = 0, fours = 0, eights = 0;
-  uint32_t hi[7] = {0, 0, 0, 0, 0, 0, 0};         // bits 4..10 of the 32 counters
-  uint32_t pend = 0;                               // a word of weight 8 waiting for a partner
-  bool have_pend = false;                          // wave-uniform
-  __device__ __forceinline__ void add_sixteens(uint32_t carry) {
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-      const uint32_t t = hi[k] & carry;
-      hi[k] ^= carry;
-      carry = t;
-    }
-  }
-  // a word of weight 8: two of them and the running eights go through one more carry-save adder, so the ripple into
-  // the high bits runs once per 16 loaded words
-  __device__ __forceinline__ void add_eights(uint32_t e) {
-    if (!have_pend) {
-      pend = e;
-      have_pend = true;
-    } else {
-      uint32_t c;
-      csa(c, eights, eights, pend, e);
-      add_sixteens(c);
-      have_pend = false;
-    }
-  }
-  __device__ __forceinline__ void finish() {
-    if (have_pend) {
-      const uint32_t c = eights & pend;
-      eights ^= pend;
-      add_sixteens(c);
-      have_pend = false;
-    }
-  }
-  __device__ __forceinline__ void add8(const uint32_t (&x)[8]) {
-    uint32_t ta, tb, fa, fb, e;
-    csa(ta, ones, ones, x[0], x[1]);
-    csa(tb, ones, ones, x[2], x[3]);
-    csa(fa, twos, twos, ta, tb);
-    csa(ta, ones, ones, x[4], x[5]);
-    csa(tb, ones, ones, x[6], x[7]);
-    csa(fb, twos, twos, ta, tb);
-    csa(e, fours, fours, fa, fb);
-    add_eights(e);
-  }
-  __device__ __forceinline__ void add4(const uint32_t (&x)[4]) {
-    uint32_t ta, tb, fa;
-    csa(ta, ones, ones, x[0], x[1]);
-    csa(tb, ones, ones, x[2], x[3]);
-    csa(fa, twos, twos, ta, tb);
-    const uint32_t e = fours & fa;
-    fours ^= fa;
-    add_eights(e);
-  }
-  // all 32 counters at once (after finish()): out[p] = counter of bit position p.  A 32 x 32 bit-matrix transpose
-  // (five rounds of masked swaps) of the 11 planes; the 21 zero rows fold away at compile time: about a third of
-  // extracting every bit of every counter on its own.
-  __device__ __forceinline__ void unslice(uint32_t (&out)[32]) const {
-    out[0] = ones; out[1] = twos; out[2] = fours; out[3] = eights;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) out[4 + k] = hi[k];
-#pragma unroll
-    for (int k = 11; k < 32; ++k) out[k] = 0u;
-    uint32_t m = 0x0000FFFFu;
-#pragma unroll
-    for (int j = 16; j != 0; j >>= 1) {
-#pragma unroll
-      for (int k = 0; k < 32; k = (k + j + 1) & ~j) {
-        const uint32_t t = ((out[k] >> j) ^ out[k + j]) & m;
-        out[k] ^= t << j;
-        out[k + j] ^= t;
-      }
-      m ^= m << (j >> 1);
-    }
-  }
-};
+constexpr int kFullTrip = 16;       // full slabs per trip of their sweep (Sliced::add16)
+constexpr int kCrossTrip = 8;       // crossing slabs per trip of theirs (Sliced::add8)
+static_assert(kP16Super % kFullTrip == 0 && kP16Super % kCrossTrip == 0, "the lists are padded to whole trips inside their LDS");
 
 // GROUPED: a material-group pass (ids = codes 0..3 of one group of three materials): raw accumulators (units of u) go to
 // acc_out[(mat_base + code) * n_rays + ray], no detection (dexct_siddon_project_grouped_packed).
@@ -224,58 +145,56 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
       n_full = max(n_full, __builtin_amdgcn_readlane(run_f, k * lpp));
       n_cross = max(n_cross, __builtin_amdgcn_readlane(run_c, k * lpp));
     }
-    n_full = (n_full + 7) & ~7;
-    n_cross = (n_cross + 3) & ~3;
+    n_full = (n_full + kFullTrip - 1) & ~(kFullTrip - 1);
+    n_cross = (n_cross + kCrossTrip - 1) & ~(kCrossTrip - 1);
     for (int k = run_f + li; k < n_full; k += lpp) list_full[g][k] = kOob;
     for (int k = run_c + li; k < n_cross; k += lpp) list_cross[g][k] = CrossRec{kOob, kOob, 0.0f, 0u};
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
-    // ---- full slabs: 8 dword loads (16 rows each) in flight, seven carry-save adders
-    for (int k = 0; k < n_full; k += 8) {
-      uint32_t x[8];
+    // ---- full slabs: 16 dword loads (16 rows each) in flight, fifteen carry-save adders and one ripple
+    for (int k = 0; k < n_full; k += kFullTrip) {
+      uint32_t x[kFullTrip];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) x[q] = ld16(list_full[g][k + q]);
+      for (int q = 0; q < kFullTrip; ++q) x[q] = ld16(list_full[g][k + q]);
       __builtin_amdgcn_sched_barrier(0);
-      cnt.add8(x);
+      cnt.add16(x);
       if (BOTH) {
-        uint32_t b[8];
+        uint32_t b[kFullTrip];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) b[q] = x[q] & (x[q] >> 1);
-        cnt3.add8(b);
+        for (int q = 0; q < kFullTrip; ++q) b[q] = x[q] & (x[q] >> 1);
+        cnt3.add16(b);
       }
     }
-    // ---- crossing slabs (and the edge slabs): count the b voxel, correct where the two voxels differ
-    for (int k = 0; k < n_cross; k += 4) {
-      uint32_t xa[4], xb[4];
-      float t4[4];
+    // ---- crossing slabs (and the edge slabs): count the b voxel, correct where the two voxels differ (in slab order)
+    for (int k = 0; k < n_cross; k += kCrossTrip) {
+      uint32_t xa[kCrossTrip], xb[kCrossTrip];
+      float t8[kCrossTrip];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      for (int j = 0; j < kCrossTrip; ++j) {
         const CrossRec q = list_cross[g][k + j];
         xa[j] = ld16(q.offa);
         xb[j] = ld16(q.offb);
-        t4[j] = q.t;
+        t8[j] = q.t;
       }
       __builtin_amdgcn_sched_barrier(0);
-      cnt.add4(xb);
+      cnt.add8(xb);
       if (BOTH) {
-        uint32_t b[4];
+        uint32_t b[kCrossTrip];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) b[j] = xb[j] & (xb[j] >> 1);
-        cnt3.add4(b);
+        for (int j = 0; j < kCrossTrip; ++j) b[j] = xb[j] & (xb[j] >> 1);
+        cnt3.add8(b);
       }
       uint32_t any = 0;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) any |= xa[j] ^ xb[j];
+      for (int j = 0; j < kCrossTrip; ++j) any |= xa[j] ^ xb[j];
       if (any) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (xa[j] != xb[j]) correct(xa[j], xb[j], t4[j]);
+        for (int j = 0; j < kCrossTrip; ++j)
+          if (xa[j] != xb[j]) correct(xa[j], xb[j], t8[j]);
       }
     }
     __builtin_amdgcn_wave_barrier();
   }
-  cnt.finish();
-  if (BOTH) cnt3.finish();
   // STAGED (the usual case: row-fastest output, whole groups of 4 rows, one or two spectra): each detection round leaves
   // its results in LDS and the wave stores them at the end, so that one store instruction writes 1 KiB of consecutive
   // addresses (whole lines) instead of 64 separate 16-byte pieces per round - every lane's 64 output bytes used to
