@@ -19,6 +19,7 @@ SYMBOLS = ['dexct_strerror', 'dexct_abi_version', 'dexct_last_hip_error', 'dexct
            'dexct_gn_reduced_rows', 'dexct_gn_decompose_multi', 'dexct_gn_covariance', 'dexct_cov_quadform',
            'dexct_fbp_var_filter', 'dexct_fbp_var_backproject', 'dexct_fdk_var_backproject',
            'dexct_cov_precision', 'dexct_pwls_majorizer', 'dexct_pwls_residual', 'dexct_pwls_update',
+           'dexct_volume_air_columns', 'dexct_siddon_project_packed_skip',
            'dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes', 'dexct_gn_multi_workspace_bytes', 'dexct_gn_cov_workspace_bytes']
 # the size queries return int64_t; dexct_strerror a string; every other entry point an int status
 SIZE_QUERIES = ['dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes', 'dexct_gn_multi_workspace_bytes',
@@ -170,6 +171,8 @@ def load():
     lib.dexct_volume_groups_pack2.argtypes = [vp, i64, i32, vp, vp]
     lib.dexct_siddon_project_packed.argtypes = [C.POINTER(FanGeom), vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp,
                                                 vp, vp, vp]
+    lib.dexct_volume_air_columns.argtypes = [vp, i32, i32, i32, vp, vp, vp]
+    lib.dexct_siddon_project_packed_skip.argtypes = lib.dexct_siddon_project_packed.argtypes[:-1] + [vp, i64, vp]
     lib.dexct_cone_layout.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.dexct_cone_project_rows.argtypes = [C.POINTER(FanGeom), vp, vp, vp, vp, f64, f64, i32, i32, vp, i32, i32, i32, vp, vp, vp,
                                             vp, vp, vp, vp, vp, vp]

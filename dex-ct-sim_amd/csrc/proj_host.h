@@ -7,6 +7,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "proj_pure.h"
 #include "siddon_detect.h"
 
 namespace dexct {
@@ -151,10 +152,15 @@ constexpr Knob kViewTileP16{"DEXCT_VIEW_TILE", 16, 1, 4096};
 constexpr Knob kRaysBatch{"DEXCT_RAYS_BATCH", 4, INT_MIN, INT_MAX};
 // rows16_kernel: skip detection FMAs of spectrum slots with zero weights (blocks of four energies); 0 = off
 constexpr Knob kDetMasks{"DEXCT_DET_MASKS", 1, INT_MIN, INT_MAX};
+// rows16_kernel, 3 and 4 materials: a wave whose rays all miss the last material runs the detection of one material less; 0 = off
+constexpr Knob kDetAbsent{"DEXCT_DET_ABSENT", 1, INT_MIN, INT_MAX};
 // rows16_kernel: store the results of a wave through LDS as whole lines; 0 = per-round 16-B stores
 constexpr Knob kP16Staged{"DEXCT_P16_STAGED", 1, INT_MIN, INT_MAX};
 // rows16_kernel, three materials: waves per SIMD the register allocation must allow; acts on 5 / 6 / 8
 constexpr Knob kP16MinW{"DEXCT_P16_MINW", 4, INT_MIN, INT_MAX};
+// rows16_kernel, the air-column map of dexct_siddon_project_packed_skip: 0 = never used, 1 = used when use_air_map
+// (proj_pure.h) says it pays, 2 = used whenever the caller passes one
+constexpr Knob kP16AirSkip{"DEXCT_P16_AIR_SKIP", 1, 0, 2};
 // cone row kernels, views per tile of the block order: 1 = all channels of a view before the next view (round 3: 9.6 ->
 // 9.2 ms on a 100-view scan, whose views 3.6 degrees apart share no columns; no difference at 0.36 degrees)
 constexpr Knob kConeViewTile{"DEXCT_CONE_VIEW_TILE", 1, 1, INT_MAX};

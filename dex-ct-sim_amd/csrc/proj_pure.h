@@ -1,0 +1,26 @@
+// Decisions of the projection host layer that are pure functions of integers: no HIP, no environment, nothing but <stdint.h>, so
+// that a stand-alone host program can run them (tests/air_map_host.cpp, also under the sanitizers).  proj_host.h includes this.
+#pragma once
+#include <stdint.h>
+
+namespace dexct {
+namespace proj {
+
+// ---- the air-column map of rows16_kernel (dexct_siddon_project_packed_skip): whether a launch looks columns up in it.
+// mode: DEXCT_P16_AIR_SKIP (knob::kP16AirSkip) - 0 never, 1 when it pays, 2 whenever there is a map.  The lookup costs every
+// slab of every lane a few instructions and gives back the sweeps of the slabs it drops, so in mode 1 the map is used from
+// a share of all-air columns on: kAirMapShareNum / kAirMapShareDen of the n_cols columns (profiles/rows16_air_skip.md has the
+// two measurements the share comes from: on 512^3 the lookup costs 0.15 ms of 10.3 where no column is air and gains 0.56 ms
+// of 9.6 where 49.6 % are, so it breaks even near one column in ten).  Counts outside 0..n_cols never use the map.
+constexpr int64_t kAirMapShareNum = 1, kAirMapShareDen = 8;
+inline bool use_air_map(int mode, bool have_map, int64_t n_air_columns, int64_t n_cols) {
+  if (!have_map || mode == 0 || n_cols <= 0 || n_air_columns < 0 || n_air_columns > n_cols) return false;
+  if (mode == 2) return true;
+  // the smallest count that reaches the share, ceil(n_cols * num / den), formed without a product of n_cols
+  const int64_t first = (n_cols / kAirMapShareDen) * kAirMapShareNum +
+                        ((n_cols % kAirMapShareDen) * kAirMapShareNum + kAirMapShareDen - 1) / kAirMapShareDen;
+  return n_air_columns >= first;
+}
+
+}  // namespace proj
+}  // namespace dexct

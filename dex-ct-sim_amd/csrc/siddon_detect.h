@@ -56,12 +56,16 @@ struct PackedArgs {
   int n_zchunks;           // ceil(n_rows / 1024)
   int view_tile;
   int det_masks;           // skip detection FMAs of spectrum slots with zero weights (blocks of four energies)
+  int det_absent;          // detect waves whose rays all miss the last material without it (DEXCT_DET_ABSENT=0: off)
   int staged_store;        // store the results of a wave through LDS as whole lines (DEXCT_P16_STAGED=0: per-round 16-B stores)
   // quantum noise (the NOISY instantiations; ABI 6): the kernel detects the variance with the counts and, `sample` != 0, draws
   // the sample itself (noise_sample.h; the Philox counter needs the GLOBAL view)
   int view_begin;
   int sample;
   uint32_t seed_lo, seed_hi;
+  // air-column map (dexct_volume_air_columns): bit y * nx + x set = column (x, y) of vol_z2 is 0 over all z; the classification
+  // enters no slab whose pieces inside the grid all lie in such columns.  Null: every slab is entered.
+  const uint32_t* col_air;
 };
 
 // The attenuation and weight tables are passed as DIRECT __restrict__ kernel arguments (not inside
@@ -91,6 +95,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 struct BlockMasks {
   unsigned long long m[2];
   bool use;                 // false: every block runs every slot (the plain loop, no branches)
+  // detect_store<.., SHORT>: the last material's row of mu is finite throughout (row_finite) and the caller wants waves whose
+  // rays all miss that material detected without it
+  bool drop_last = false;
 };
 
 __device__ __forceinline__ BlockMasks detect_block_masks(const float* __restrict__ w, int n_e, int n_spectra) {
@@ -107,6 +114,13 @@ __device__ __forceinline__ BlockMasks detect_block_masks(const float* __restrict
     bm.m[s] = s < n_spectra ? __ballot(nz) : 0ull;
   }
   return bm;
+}
+
+// Whether a table row holds finite values only.  Once per wave, which every lane must reach (ballot), like detect_block_masks.
+__device__ __forceinline__ bool row_finite(const float* __restrict__ row, int n_e) {
+  bool fin = true;
+  for (int e = threadIdx.x & (kWave - 1); e < n_e; e += kWave) fin = fin && (__float_as_uint(row[e]) & 0x7F800000u) != 0x7F800000u;
+  return __ballot(!fin) == 0ull;
 }
 
 // VAR (round 6): every slot also accumulates the VARIANCE of its signal, sum_e w2[s][e] 2^(...), from the same exponentials -
@@ -300,7 +314,10 @@ struct AirCache {
 // FVAR (with res_out and var_out, at most two spectra): the variances sum_e w2[s][e] exp(-...) come out of the same energy
 // loop as the counts (detect_energies<.., VAR>) and are handed to the caller like the counts - the kernels that draw the
 // noise sample themselves.  Same bits as the separate loop below.
-template <int NM, int R, bool EXTRAS = true, bool FVAR = false>
+// SHORT (R = 4, NM >= 3, at most two spectra; bm.drop_last): a wave none of whose rays crosses the LAST material runs the energy
+// loop of NM - 1 materials.  The last exponent FMA of such a ray is fma(mu, 0, pe) = pe for finite mu (pe is never -0: its
+// chain starts from +0), so every exponent, and with it every sum, keeps its bits; one v_pk_fma_f32 per pair and energy less.
+template <int NM, int R, bool EXTRAS = true, bool FVAR = false, bool SHORT = false>
 __device__ __forceinline__ void detect_store(const float (&L)[R][NM], const ProjArgs& a, const float* __restrict__ mu,
                                              const float* __restrict__ w, const float* __restrict__ w2,
                                              const size_t (&ray)[R], const bool (&valid)[R],
@@ -358,6 +375,15 @@ __device__ __forceinline__ void detect_store(const float (&L)[R][NM], const Proj
       wave_air = __ballot(!lane_air) == 0ull;
     }
   }
+  bool wave_short = false;
+  if constexpr (SHORT && R == 4 && NM >= 3) {
+    if (a.n_spectra <= 2 && bm.drop_last && !wave_air) {
+      bool lane_none = true;
+#pragma unroll
+      for (int q = 0; q < R; ++q) lane_none = lane_none && L[q][NM - 1] == 0.0f;
+      wave_short = __ballot(!lane_none) == 0ull;
+    }
+  }
   if (wave_air) {
     float one[DEXCT_MAX_SPECTRA][1], onev[DEXCT_MAX_SPECTRA][1];
     bool cached = false;
@@ -383,6 +409,16 @@ __device__ __forceinline__ void detect_store(const float (&L)[R][NM], const Proj
       acc[0][q] = one[0][0];
       acc[1][q] = one[1][0];
       if constexpr (FVAR) { accv[0][q] = onev[0][0]; accv[1][q] = onev[1][0]; }
+    }
+  } else if (wave_short) {
+    if constexpr (SHORT && R == 4 && NM >= 3) {
+      f32x2 Ls[(R + 1) / 2][NM - 1];
+#pragma unroll
+      for (int j = 0; j < (R + 1) / 2; ++j)
+#pragma unroll
+        for (int m = 0; m < NM - 1; ++m) Ls[j][m] = Lp[j][m];
+      if constexpr (FVAR) detect_energies<NM - 1, R, 2, true>(Ls, mu, w, n_e, srow, bm, acc, w2, &accv);
+      else detect_energies<NM - 1, R, 2>(Ls, mu, w, n_e, srow, bm, acc);
     }
   } else if constexpr (FVAR)
     detect_energies<NM, R, 2, true>(Lp, mu, w, n_e, srow, bm, acc, w2, &accv);

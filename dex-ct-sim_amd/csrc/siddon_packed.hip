@@ -21,6 +21,11 @@
 // Lanes: a pair of n_rows rows needs n_rows / 16 lanes.  For n_rows / 16 < 64 a wave carries 64 / (n_rows / 16)
 // neighbouring channels of one view (per-lane pair index; each pair has its own slab lists in LDS and list entries
 // beyond a pair's count point outside the buffer, which reads as air and counts nothing).
+//
+// Air columns.  A column (x, y) that is air over all z is a run of zero words: it adds nothing to a counter and never differs
+// from another such column.  dexct_volume_air_columns marks these columns in a bit map (once per volume) and the SKIP forms of
+// the kernel (dexct_siddon_project_packed_skip) enter no slab in their lists whose pieces all lie in marked columns: the sweeps
+// get shorter, every sum keeps its bits (profiles/rows16_air_skip.md).
 #include "common.h"
 #include "noise_sample.h"
 #include "proj_host.h"
@@ -32,6 +37,8 @@ constexpr int kP16Super = 128;      // slabs staged per pass
 constexpr uint32_t kOob = 0xF0000000u;   // a list offset outside every buffer (< 3.75 GiB): the load returns 0 (air), no traffic
 constexpr int kFullTrip = 16;       // full slabs per trip of their sweep (Sliced::add16)
 constexpr int kCrossTrip = 8;       // crossing slabs per trip of theirs (Sliced::add8)
+constexpr int kAirBatch = 2;         // classification iterations whose air-map lookups fly together (kP16Super / 64 = 2 at least)
+static_assert(kP16Super % (kAirBatch * 64) == 0, "whole batches for every lane group");
 static_assert(kP16Super % kFullTrip == 0 && kP16Super % kCrossTrip == 0, "the lists are padded to whole trips inside their LDS");
 
 // GROUPED: a material-group pass (ids = codes 0..3 of one group of three materials): raw accumulators (units of u) go to
@@ -42,11 +49,16 @@ static_assert(kP16Super % kFullTrip == 0 && kP16Super % kCrossTrip == 0, "the li
 // the exponentials are shared) and, pa.sample, draw the sample in the registers that hold both (noise_sample.h: one Philox
 // block per ray serves both spectra): what leaves the kernel is the noisy sinogram - no variance array, no pass over it.
 // a.variance (optional) receives the variances as well (tests; callers that sample with dexct_add_noise).
-template <int NM, int MINW = 4, bool GROUPED = false, bool STAGED = false, bool NOISY = false>      // MINW: waves per SIMD the register allocation must allow
+// SKIP: the classification looks every slab up in the air-column map pa.col_air (dexct_siddon_project_packed_skip) and enters
+// no slab that lies in all-air columns; the forms without it are the kernels as they were.
+template <int NM, int MINW = 4, bool GROUPED = false, bool STAGED = false, bool NOISY = false, bool SKIP = false>      // MINW: waves per SIMD the register allocation must allow
 __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const float* __restrict__ mu, const float* __restrict__ w,
                                                     const float* __restrict__ w2) {
   static_assert(NM >= 2 && NM <= 4, "ids 0..3");
   constexpr bool BOTH = NM > 3;              // id 3 exists: count the "both flags" plane too
+  // detect_store<.., SHORT>: waves whose rays all miss the last material detect without it.  Not in the noisy three-material
+  // form: its 127 VGPRs leave no room (with the second energy loop it spilled 4 - 7 VGPRs to scratch)
+  constexpr bool kShort = !GROUPED && NM >= 3 && !(NOISY && NM == 3);
   extern __shared__ uint32_t lds_lists[];          // per pair: kP16Super crossing records (16 B), then kP16Super offsets
   const ProjArgs& a = pa.a;
   const int lane = threadIdx.x;
@@ -54,6 +66,7 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
   if (!GROUPED) {
     bm = detect_block_masks(w, a.n_energies, a.n_spectra);      // all 64 lanes are here
     bm.use = bm.use && pa.det_masks;
+    if (kShort) bm.drop_last = row_finite(mu + (size_t)(NM - 1) * a.n_energies, a.n_energies) && pa.det_absent;
   }
   const int lpp = pa.lanes_per_pair, n_pairs = 64 / lpp;
   CrossRec (*list_cross)[kP16Super] = reinterpret_cast<CrossRec (*)[kP16Super]>(lds_lists);
@@ -113,10 +126,57 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
   for (int k = 0; k < n_pairs; ++k) n_slabs_max = max(n_slabs_max, __builtin_amdgcn_readlane(p.n_slabs, k * lpp));
   const unsigned long long group_mask = (lpp == 64 ? ~0ull : ((1ull << lpp) - 1ull)) << (g * lpp);
   const unsigned long long below_mask = group_mask & ((1ull << lane) - 1ull);
+  static_assert(!(GROUPED && SKIP), "the group passes take no map");
   for (int s0 = 0; s0 < n_slabs_max; s0 += kP16Super) {
     // ---- geometry: the lanes of a pair classify its slabs s0 + li, s0 + li + lpp, ... (slab order kept per pair)
     int run_f = 0, run_c = 0;               // per pair (identical in all lanes of a pair)
-    for (int q0 = 0; q0 < kP16Super; q0 += lpp) {
+    // SKIP: the same classification as below, kAirBatch iterations at a time so that their map words are in
+    // flight together, and a slab whose pieces inside the grid all lie in all-air columns is entered in neither list.  Its
+    // words are 0: they add nothing to a counter and two equal words cause no correction, so every sum keeps its bits; the
+    // slabs that stay keep their order.  A crossing slab with one air piece stays (its count and its correction are needed).
+    // The offsets are column index x zb: the same integers as i * su + j * sv.
+    for (int q0 = 0; SKIP && q0 < kP16Super; q0 += kAirBatch * lpp) {
+      const uint32_t cu = axis == 0 ? 1u : (uint32_t)a.g.nx, cv = axis == 0 ? (uint32_t)a.g.nx : 1u;
+      const uint32_t last_word = ((uint32_t)a.g.nx * (uint32_t)a.g.ny - 1u) >> 5;
+      uint32_t cola[kAirBatch], colb[kAirBatch], wa[kAirBatch], wb[kAirBatch];
+      float tt[kAirBatch];
+      bool ina[kAirBatch], inb[kAirBatch], one[kAirBatch];          // one: both pieces in the same column
+#pragma unroll
+      for (int u = 0; u < kAirBatch; ++u) {
+        const int s = s0 + q0 + u * lpp + li;
+        cola[u] = colb[u] = 0u;
+        tt[u] = 0.0f;
+        ina[u] = inb[u] = one[u] = false;
+        if (s < p.n_slabs) {
+          const int i = p.i_first + s;
+          const SlabPieces sp = dda_slab(p.V0 + (long long)i * p.SV, p.SV, smask, p.kf);
+          ina[u] = (uint32_t)sp.ja < (uint32_t)nv;
+          inb[u] = (uint32_t)sp.jb < (uint32_t)nv;
+          cola[u] = (uint32_t)i * cu + (uint32_t)sp.ja * cv;
+          colb[u] = (uint32_t)i * cu + (uint32_t)sp.jb * cv;
+          one[u] = sp.ja == sp.jb;
+          tt[u] = sp.t;
+        }
+        // (a piece outside the grid, and a lane without a slab, look at word 0 and ignore it; the map is read through a plain
+        // pointer, not a bounds-checked buffer, so the word index is held inside it whatever the plan says)
+        wa[u] = pa.col_air[ina[u] ? min(cola[u] >> 5, last_word) : 0u];
+        wb[u] = pa.col_air[inb[u] ? min(colb[u] >> 5, last_word) : 0u];
+      }
+#pragma unroll
+      for (int u = 0; u < kAirBatch; ++u) {
+        const bool air_a = !ina[u] || ((wa[u] >> (cola[u] & 31u)) & 1u), air_b = !inb[u] || ((wb[u] >> (colb[u] & 31u)) & 1u);
+        const bool keep = !(air_a && air_b);
+        const bool whole = ina[u] && inb[u] && one[u];
+        const bool is_full = whole && keep, is_cross = !whole && (ina[u] || inb[u]) && keep;
+        const uint32_t offa = ina[u] ? cola[u] * zb : kOob, offb = inb[u] ? colb[u] * zb : kOob;
+        const unsigned long long mf = __ballot(is_full), mc = __ballot(is_cross);
+        if (is_full) list_full[g][run_f + __popcll(mf & below_mask)] = offb;
+        if (is_cross) list_cross[g][run_c + __popcll(mc & below_mask)] = CrossRec{offa, offb, tt[u], 0u};
+        run_f += __popcll(mf & group_mask);
+        run_c += __popcll(mc & group_mask);
+      }
+    }
+    for (int q0 = 0; !SKIP && q0 < kP16Super; q0 += lpp) {
       const int s = s0 + q0 + li;
       bool is_full = false, is_cross = false;
       uint32_t offa = kOob, offb = kOob;
@@ -288,7 +348,7 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
       }
       if constexpr (NOISY) {
         float var[2][4];
-        detect_store<NM, 4, false, true>(L, a, mu, w, w2, rays, valid, bm, &air_cache, &res, &var);
+        detect_store<NM, 4, false, true, kShort>(L, a, mu, w, w2, rays, valid, bm, &air_cache, &res, &var);
         if (a.variance && round_live) {            // (optional output: plain stores)
 #pragma unroll
           for (int s = 0; s < 2; ++s)
@@ -331,9 +391,9 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
           }
         }
       } else if constexpr (staged) {
-        detect_store<NM, 4, false>(L, a, mu, w, w2, rays, valid, bm, &air_cache, &res);
+        detect_store<NM, 4, false, false, kShort>(L, a, mu, w, w2, rays, valid, bm, &air_cache, &res);
       } else {
-        detect_store<NM, 4>(L, a, mu, w, w2, rays, valid, bm, &air_cache);
+        detect_store<NM, 4, true, false, kShort>(L, a, mu, w, w2, rays, valid, bm, &air_cache);
       }
     }
     // STAGED: the round's results go to LDS right away (plane s, float index 16 lane + row): no registers are held for
@@ -391,6 +451,37 @@ __global__ __launch_bounds__(256) void pack2_kernel(const uint8_t* __restrict__ 
   out[i] = (uint8_t)((x & 3u) | (((x >> 8) & 3u) << 2) | (((x >> 16) & 3u) << 4) | (((x >> 24) & 3u) << 6));
 }
 
+// The air-column map of the packed volume: bit c % 32 of word c / 32 is set iff the zb bytes of column c = y * nx + x are all
+// 0; the bits past the last column stay clear.  A workgroup takes 256 columns at a time (grid-stride over such chunks:
+// block-uniform, so every lane reaches the ballot); a wave's ballot is two words of the map.  n_air receives the set bits.
+__global__ __launch_bounds__(256) void col_air_kernel(const uint8_t* __restrict__ vol_z2, uint32_t n_cols, uint32_t zb,
+                                                      uint32_t* __restrict__ col_air, unsigned long long* __restrict__ n_air) {
+  const uint32_t n_chunks = (n_cols + 255u) / 256u, n_words = (n_cols + 31u) / 32u;
+  const bool dwords = (zb & 3u) == 0 && (reinterpret_cast<uintptr_t>(vol_z2) & 3u) == 0;
+  for (uint32_t ch = blockIdx.x; ch < n_chunks; ch += gridDim.x) {
+    const uint32_t col = ch * 256u + threadIdx.x;
+    uint32_t any = 1u;
+    if (col < n_cols) {
+      const uint8_t* q = vol_z2 + (size_t)col * zb;
+      any = 0u;
+      if (dwords)
+        for (uint32_t k = 0; k < zb; k += 4) any |= *reinterpret_cast<const uint32_t*>(q + k);
+      else
+        for (uint32_t k = 0; k < zb; ++k) any |= q[k];
+    }
+    const unsigned long long m = __ballot(any == 0u);
+    if ((threadIdx.x & 63u) == 0u) {
+      const uint32_t wi = (ch * 256u + threadIdx.x) >> 5;
+      if (wi < n_words) col_air[wi] = (uint32_t)m;
+      if (wi + 1 < n_words) col_air[wi + 1] = (uint32_t)(m >> 32);
+      if (m) atomicAdd(n_air, (unsigned long long)__popcll(m));
+    }
+  }
+}
+
+// the grid cap of col_air_kernel (one column per thread)
+constexpr int kColAirMaxBlocks = 4096;
+
 // Material groups on the packed volume: ids 3g+1..3g+3 -> codes 1..3, everything else 0 (group_codes_kernel of
 // siddon.hip), packed four voxels per byte: out [n_groups][n_voxels / 4]
 __global__ __launch_bounds__(256) void group_codes_pack2_kernel(const uint8_t* __restrict__ vol_zf, size_t n_bytes_out,
@@ -417,9 +508,9 @@ struct P16Launch {
   size_t lds;
   hipStream_t st;
 };
-template <int NM, int MINW, bool GROUPED, bool STAGED, bool NOISY>
+template <int NM, int MINW, bool GROUPED, bool STAGED, bool NOISY, bool SKIP = false>
 static int launch_p16(const P16Launch& l) {
-  hipLaunchKernelGGL((rows16_kernel<NM, MINW, GROUPED, STAGED, NOISY>), l.grid, dim3(64), l.lds, l.st, l.pa, l.t.mu, l.t.w, l.t.w2);
+  hipLaunchKernelGGL((rows16_kernel<NM, MINW, GROUPED, STAGED, NOISY, SKIP>), l.grid, dim3(64), l.lds, l.st, l.pa, l.t.mu, l.t.w, l.t.w2);
   DEXCT_LAUNCH_CHECK();
   return DEXCT_OK;
 }
@@ -442,6 +533,7 @@ static int packed_shape(const dexct_fan_geom* geom, int32_t view_begin, int32_t 
   pa.n_zchunks = lanes > 64 ? (lanes + 63) / 64 : 1;
   pa.view_tile = proj::read_knob(proj::knob::kViewTileP16);
   pa.det_masks = proj::read_knob(proj::knob::kDetMasks) != 0;
+  pa.det_absent = proj::read_knob(proj::knob::kDetAbsent) != 0;
   pa.staged_store = proj::read_knob(proj::knob::kP16Staged) != 0;
   pa.view_begin = view_begin;
   const int n_pairs = 64 / pa.lanes_per_pair;
@@ -450,6 +542,18 @@ static int packed_shape(const dexct_fan_geom* geom, int32_t view_begin, int32_t 
   lds = (size_t)n_pairs * kP16Super * (sizeof(CrossRec) + sizeof(uint32_t));
   if (lds < 2 * 64 * 64) lds = 2 * 64 * 64;   // the staged store of the results: 64 bytes per lane and spectrum
   return DEXCT_OK;
+}
+
+// the SKIP forms rows16_kernel<NM, MINW, false, STAGED, NOISY, true> (MINW as the forms without the map; the DEXCT_P16_MINW forms have none)
+static int launch_p16_skip(const P16Launch& l, int n_materials, bool staged, bool noisy) {
+  if (noisy) {
+    if (n_materials == 2) return staged ? launch_p16<2, 4, false, true, true, true>(l) : launch_p16<2, 4, false, false, true, true>(l);
+    if (n_materials == 4) return staged ? launch_p16<4, 3, false, true, true, true>(l) : launch_p16<4, 3, false, false, true, true>(l);
+    return staged ? launch_p16<3, 4, false, true, true, true>(l) : launch_p16<3, 4, false, false, true, true>(l);
+  }
+  if (n_materials == 2) return staged ? launch_p16<2, 4, false, true, false, true>(l) : launch_p16<2, 4, false, false, false, true>(l);
+  if (n_materials == 4) return staged ? launch_p16<4, 3, false, true, false, true>(l) : launch_p16<4, 3, false, false, false, true>(l);
+  return staged ? launch_p16<3, 4, false, true, false, true>(l) : launch_p16<3, 4, false, false, false, true>(l);
 }
 
 }  // namespace dexct
@@ -480,11 +584,35 @@ int dexct_volume_groups_pack2(const uint8_t* vol_zf, int64_t n_voxels, int32_t n
   return DEXCT_OK;
 }
 
+int dexct_volume_air_columns(const uint8_t* vol_z2, int32_t nx, int32_t ny, int32_t nz, uint32_t* col_air, uint64_t* n_air,
+                             void* stream) {
+  if (!vol_z2 || !col_air || !n_air || nx < 1 || ny < 1 || nz < 4 || (nz & 3)) return DEXCT_EINVAL;
+  if ((uint64_t)nx * ny > 0x7FFFFF00ull) return DEXCT_ERANGE;                 // 32-bit column indices (whole chunks of 256)
+  const uint32_t n_cols = (uint32_t)nx * (uint32_t)ny;
+  hipStream_t st = as_stream(stream);
+  DEXCT_HIP_TRY(hipMemsetAsync(n_air, 0, sizeof(uint64_t), st));
+  uint32_t nblk = (n_cols + 255u) / 256u;
+  if (nblk > (uint32_t)kColAirMaxBlocks) nblk = kColAirMaxBlocks;
+  hipLaunchKernelGGL(col_air_kernel, dim3(nblk), dim3(256), 0, st, vol_z2, n_cols, (uint32_t)nz >> 2, col_air,
+                     reinterpret_cast<unsigned long long*>(n_air));
+  DEXCT_LAUNCH_CHECK();
+  return DEXCT_OK;
+}
+
 int dexct_siddon_project_packed(const dexct_fan_geom* geom, const dexct_ray_plan* plan, int32_t view_begin,
                                 int32_t view_end, const uint8_t* vol_z2, int32_t n_materials, int32_t n_energies,
                                 int32_t n_spectra, const float* mu, const float* weights, float* counts, float* pathlen,
                                 int32_t layout, const dexct_log_out* log_out, const float* weights2, float* variance,
                                 const dexct_noise* noise, void* stream) {
+  return dexct_siddon_project_packed_skip(geom, plan, view_begin, view_end, vol_z2, n_materials, n_energies, n_spectra, mu, weights,
+                                          counts, pathlen, layout, log_out, weights2, variance, noise, nullptr, 0, stream);
+}
+
+int dexct_siddon_project_packed_skip(const dexct_fan_geom* geom, const dexct_ray_plan* plan, int32_t view_begin,
+                                     int32_t view_end, const uint8_t* vol_z2, int32_t n_materials, int32_t n_energies,
+                                     int32_t n_spectra, const float* mu, const float* weights, float* counts, float* pathlen,
+                                     int32_t layout, const dexct_log_out* log_out, const float* weights2, float* variance,
+                                     const dexct_noise* noise, const uint32_t* col_air, int64_t n_air_columns, void* stream) {
   if (!geom || !plan || !vol_z2 || !mu || !weights || !counts) return DEXCT_EINVAL;
   if (n_energies < 1 || n_spectra < 1) return DEXCT_EINVAL;
   if (n_materials < 2 || n_materials > 4 || n_spectra > DEXCT_MAX_SPECTRA) return DEXCT_ERANGE;     // ids 0..3
@@ -498,7 +626,11 @@ int dexct_siddon_project_packed(const dexct_fan_geom* geom, const dexct_ray_plan
                                 nl);
   l.pa.a.view_tile = l.pa.view_tile;
   l.pa.vol_z2 = vol_z2;
-  proj::copy_noise(l.pa, view_begin, nl);      // (rows16_kernel draws the sample itself: PackedArgs, not its ProjArgs)
+  const int64_t n_cols = (int64_t)geom->nx * geom->ny;
+  if (col_air && (n_air_columns < 0 || n_air_columns > n_cols)) return DEXCT_EINVAL;
+  // the map costs a few instructions per slab and lane and pays them back with the slabs it drops: proj::use_air_map
+  l.pa.col_air = proj::use_air_map(proj::read_knob(proj::knob::kP16AirSkip), col_air != nullptr, n_air_columns, n_cols) ? col_air : nullptr;
+  proj::copy_noise(l.pa, view_begin, nl);     // (rows16_kernel draws the sample itself: PackedArgs, not its ProjArgs)
   l.t = Tables{mu, weights, weights2};
   l.st = as_stream(stream);
   const bool noisy = weights2 != nullptr;
@@ -507,6 +639,13 @@ int dexct_siddon_project_packed(const dexct_fan_geom* geom, const dexct_ray_plan
   const bool staged = l.pa.staged_store && layout == 1 && geom->n_rows % 4 == 0 && n_spectra <= 2;
   // rows16_kernel<NM, MINW, false, STAGED, NOISY>: MINW is 4 for two and three materials, 3 for four.  (The order of the arms
   // is the order in which the kernels are instantiated, hence their order in the code object.)
+  // with the air-column map: the SKIP forms (instantiated after all the others, below); the DEXCT_P16_MINW forms have none
+  // three materials without noise also have the forms DEXCT_P16_MINW asks for: 5 with and without the staged store, 6 and 8
+  // without; every other value is 4 - and any value but 4 and 5 has always cost the staged store
+  const int minw = (noisy || n_materials != 3) ? 4 : proj::read_knob(proj::knob::kP16MinW);
+  const bool minw_form = minw == 5 || minw == 6 || minw == 8;
+  // with the air-column map: the SKIP forms, which exist for the default MINW only
+  if (l.pa.col_air && !minw_form) return launch_p16_skip(l, n_materials, staged && minw == 4, noisy);
   if (noisy) {
     if (n_materials == 2) return staged ? launch_p16<2, 4, false, true, true>(l) : launch_p16<2, 4, false, false, true>(l);
     if (n_materials == 4) return staged ? launch_p16<4, 3, false, true, true>(l) : launch_p16<4, 3, false, false, true>(l);
@@ -514,9 +653,6 @@ int dexct_siddon_project_packed(const dexct_fan_geom* geom, const dexct_ray_plan
   }
   if (n_materials == 2) return staged ? launch_p16<2, 4, false, true, false>(l) : launch_p16<2, 4, false, false, false>(l);
   if (n_materials == 4) return staged ? launch_p16<4, 3, false, true, false>(l) : launch_p16<4, 3, false, false, false>(l);
-  // three materials without noise also have the forms DEXCT_P16_MINW asks for: 5 with and without the staged store, 6 and 8
-  // without; every other value is 4 - and any value but 4 and 5 has always cost the staged store
-  const int minw = proj::read_knob(proj::knob::kP16MinW);
   if (staged && minw == 4) return launch_p16<3, 4, false, true, false>(l);
   if (minw == 5) return staged ? launch_p16<3, 5, false, true, false>(l) : launch_p16<3, 5, false, false, false>(l);
   if (minw == 6) return launch_p16<3, 6, false, false, false>(l);

@@ -196,11 +196,18 @@ class Projector:
         self.vol_zf = torch.empty_like(self.vol_yx) if row_parallel else None
         _native.check(self.lib.dexct_volume_layouts(ptr(self.vol_yx), phantom.Nx, phantom.Ny, nz,
                                                     ptr(self.vol_xy), ptr(self.vol_zf), st), 'dexct_volume_layouts')
-        self.vol_z2 = None
+        self.vol_z2, self.col_air, self.n_air_columns = None, None, 0
         if self.use_packed:
             self.vol_z2 = torch.empty(self.vol_zf.numel() // 4, dtype=torch.uint8, device=self.dev)
             _native.check(self.lib.dexct_volume_pack2(ptr(self.vol_zf), self.vol_zf.numel(), ptr(self.vol_z2), st),
                           'dexct_volume_pack2')
+            # its air-column map (one bit per (x, y) column that is air over all z) and the number of such columns: the
+            # packed kernel enters no slab that lies in them; the library decides per call whether looking them up pays
+            self.col_air = torch.empty((phantom.Nx * phantom.Ny + 31) // 32, dtype=torch.int32, device=self.dev)
+            n_air = torch.empty(1, dtype=torch.int64, device=self.dev)
+            _native.check(self.lib.dexct_volume_air_columns(ptr(self.vol_z2), phantom.Nx, phantom.Ny, nz, ptr(self.col_air),
+                                                            ptr(n_air), st), 'dexct_volume_air_columns')
+            self.n_air_columns = int(n_air.item())
         # ---- 6. group codes of the material-group passes
         aligned = nz % 4 == 0 and z_first % 4 == 0
         self.grouped = not self.grouped_packed and (kernel == 4 or (kernel == 0 and row_parallel and M > 4 and aligned))
@@ -427,9 +434,9 @@ class Projector:
                 geom, c.plan_ptr, *self._cone_rays(), c.vb, ve, ptr(self.vol_yx), ptr(self.vol_xy), M, c.nE, c.S, c.mu, c.w,
                 ptr(counts), ptr(pathlen), lo, c.w2, ptr(variance), c.nz, stream_ptr()), 'dexct_cone_project')
         elif c.packed:                                          # (noise on > 2 spectra: the byte-volume kernel below)
-            _native.check(lib.dexct_siddon_project_packed(
+            _native.check(lib.dexct_siddon_project_packed_skip(
                 geom, c.plan_ptr, c.vb, ve, ptr(self.vol_z2), M, c.nE, c.S, c.mu, c.w, ptr(counts), ptr(pathlen), c.run_layout, lo,
-                c.w2, ptr(variance), c.nz, stream_ptr()), 'dexct_siddon_project_packed')
+                c.w2, ptr(variance), c.nz, ptr(self.col_air), self.n_air_columns, stream_ptr()), 'dexct_siddon_project_packed_skip')
         else:
             _native.check(lib.dexct_siddon_project(
                 geom, c.plan_ptr, c.vb, ve, ptr(self.vol_yx), ptr(self.vol_xy), ptr(self.vol_zf), M, c.nE, c.S, c.mu, c.w,

@@ -215,6 +215,25 @@ int dexct_siddon_project_packed(const dexct_fan_geom* geom, const dexct_ray_plan
                                 float* pathlen, int32_t layout, const dexct_log_out* log_out, const float* weights2,
                                 float* variance, const dexct_noise* noise, void* stream);
 
+/* The air-column map of a packed volume, and the packed projection that uses it (additive: ABI 6 still).
+ * dexct_volume_air_columns: col_air[(nx*ny + 31) / 32] words: bit (y*nx + x) % 32 of word (y*nx + x) / 32 is set iff all
+ *   nz/4 bytes of column (x, y) of vol_z2 are 0 (air over all z); the bits past the last column are clear.  *n_air (device
+ *   memory, like col_air) receives the number of set bits.  nz a multiple of 4; nx*ny < 2^31.  The map belongs to the
+ *   volume: it is built once, next to vol_z2.
+ * dexct_siddon_project_packed_skip: dexct_siddon_project_packed with that map (col_air, and the count the builder gave,
+ *   n_air_columns).  The kernel then leaves out every slab whose pieces inside the grid all lie in all-air columns: such
+ *   a slab counts nothing and corrects nothing, so EVERY output keeps its bits.  Looking a slab up costs a little even
+ *   where nothing is air: DEXCT_P16_AIR_SKIP (read on every call) = 1 (default) uses the map from a share of air columns
+ *   on, 2 whenever one is passed, 0 never.  col_air null = dexct_siddon_project_packed (n_air_columns ignored). */
+int dexct_volume_air_columns(const uint8_t* vol_z2, int32_t nx, int32_t ny, int32_t nz, uint32_t* col_air, uint64_t* n_air,
+                             void* stream);
+int dexct_siddon_project_packed_skip(const dexct_fan_geom* geom, const dexct_ray_plan* plan, int32_t view_begin,
+                                     int32_t view_end, const uint8_t* vol_z2, int32_t n_materials, int32_t n_energies,
+                                     int32_t n_spectra, const float* mu, const float* weights, float* counts,
+                                     float* pathlen, int32_t layout, const dexct_log_out* log_out, const float* weights2,
+                                     float* variance, const dexct_noise* noise, const uint32_t* col_air,
+                                     int64_t n_air_columns, void* stream);
+
 /* Material groups on the packed volume (5..DEXCT_MAX_MATERIALS materials; the packed form of dexct_volume_groups /
  * dexct_siddon_project_grouped, same arguments and outputs; preconditions of dexct_siddon_project_packed).
  * dexct_volume_groups_pack2: codes2[g][n_voxels / 4]: the group codes 0..3 of dexct_volume_groups at 2 bits per voxel.
