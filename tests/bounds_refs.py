@@ -210,7 +210,7 @@ class Scan:
     uint8 volume [nz][ny][nx] of ids 0 .. n_mat - 1 and the float32 tables mu [M][n_e], w / w2 [S][n_e]."""
 
     def __init__(self, nx, ny, nz, n_views, n_ch, n_rows, z_first=0, n_mat=3, n_e=5, n_spec=2, fan=0.16, seed=0, air=False,
-                 dx=0.31, dy=0.27, dz=0.4, sid=SID, sdd=SDD, cone_h=None, src_z=0.0, theta0=0.0):
+                 dx=0.31, dy=0.27, dz=0.4, sid=SID, sdd=SDD, cone_h=None, src_z=0.0, theta0=0.0, row_centre=None):
         rng = np.random.default_rng(seed * 1000 + nx * 7 + ny * 3 + nz + n_mat)
         self.nx, self.ny, self.nz, self.n_views, self.n_ch, self.n_rows, self.z_first = nx, ny, nz, n_views, n_ch, n_rows, z_first
         self.n_mat, self.n_e, self.n_spec = n_mat, n_e, n_spec
@@ -235,6 +235,8 @@ class Scan:
         self.cone = cone_h is not None
         self.src_z = src_z
         self.row_z = (np.arange(n_rows) - 0.5 * (n_rows - 1)) * cone_h if self.cone else None
+        if row_centre is not None:                                       # the rows centred on another height than 0
+            self.row_z = self.row_z + row_centre
 
     def geom(self, make):
         """``make``: c_oracle.make_geom or a constructor of _native.FanGeom with the same twelve numbers."""
@@ -319,6 +321,124 @@ SCANS['cone_tall'] = dict(SCANS['cone'], cone_h=3.0, theta0=0.05)
 SCANS['cone_m2'] = dict(SCANS['cone'], n_mat=2)
 SCANS['cone1040_m2'] = dict(SCANS['cone1040'], n_mat=2)
 SCANS['cone1040_m1'] = dict(SCANS['cone1040'], n_mat=1)
+
+
+# ---- cone scans at the edge of the slope contract -------------------------------------------------------------------------------
+# proj::cone_slope_ok (csrc/proj_host.h) accepts a cone scan when f = max_abs_dz / sdd / dz * max(dx, dy) * sqrt(2) <= 1: no ray
+# climbs more than one slice per dominant-axis slab.  The scans above have f <= 0.15; those below have max_abs_dz EQUAL to the
+# largest float64 the predicate accepts (edge90: 0.9 of it).  In slices per slab a ray climbs |sw| = f hypot(dx, dy) /
+# (sqrt(2) max(dx, dy)) at the most, at the dominant-axis switch, so only dx = dy reaches one slice per slab: edge_aniso keeps
+# dy within 1 % of dx (|sw| <= 0.995) and takes its anisotropy from dz.  Odd nx, ny and channel counts: the central ray of an
+# axis-aligned view runs through the middle of a voxel row, not along a grid plane.
+
+SQRT2 = 1.4142135623730951
+
+
+def slope_ok(max_abs_dz, dx, dy, dz, sdd):
+    """proj::cone_slope_ok restated: the same float64 operations in the same order."""
+    dmax = dx if dx > dy else dy
+    return max_abs_dz >= 0 and not (max_abs_dz / sdd / dz * dmax * SQRT2 > 1.0)
+
+
+def slope_limit(dx, dy, dz, sdd):
+    """The largest float64 max_abs_dz that slope_ok accepts."""
+    m = sdd * dz / (max(dx, dy) * SQRT2)
+    while not slope_ok(m, dx, dy, dz, sdd):
+        m = float(np.nextafter(m, -np.inf))
+    while slope_ok(float(np.nextafter(m, np.inf)), dx, dy, dz, sdd):
+        m = float(np.nextafter(m, np.inf))
+    return m
+
+
+def _row_reach(n_rows, cone_h, src_z, row_centre):
+    """max_abs_dz of a Scan with these rows (the operations of Scan.__init__ and Scan.max_abs_dz)."""
+    row_z = (np.arange(n_rows) - 0.5 * (n_rows - 1)) * cone_h
+    if row_centre is not None:
+        row_z = row_z + row_centre
+    return float(np.max(np.abs(row_z - src_z)))
+
+
+def _edge(share=1.0, **kw):
+    """Scan arguments whose row pitch makes max_abs_dz exactly ``share`` of the slope limit (share 1: the limit itself, to the
+    last bit: the pitch next to limit / half_rows whose rounded row heights give it)."""
+    kw = dict(dict(nx=21, ny=17, nz=96, n_views=8, n_ch=15, n_rows=17, dx=0.2, dy=0.2, dz=0.2, sid=9.0, sdd=16.0, theta0=np.pi / 4), **kw)
+    limit = slope_limit(kw['dx'], kw['dy'], kw['dz'], kw['sdd'])
+    src_z, centre, n_rows = kw.get('src_z', 0.0), kw.get('row_centre'), kw['n_rows']
+    h = share * limit / (0.5 * (n_rows - 1))
+    if share == 1.0:
+        lo = hi = h
+        for _ in range(256):
+            if _row_reach(n_rows, lo, src_z, centre) == limit or _row_reach(n_rows, hi, src_z, centre) == limit:
+                break
+            lo, hi = float(np.nextafter(lo, -np.inf)), float(np.nextafter(hi, np.inf))
+        h = lo if _row_reach(n_rows, lo, src_z, centre) == limit else hi
+        assert _row_reach(n_rows, h, src_z, centre) == limit, kw
+    return dict(kw, cone_h=h)
+
+
+_TALL = dict(nx=11, ny=9, n_ch=5, n_rows=33, dz=0.05, src_z=0.3, row_centre=0.3)        # as cone256 .. cone1040, steep
+EDGE_SCANS = {
+    # diagonal views with |ex| == |ey| and axis-aligned ones; the outermost rows stay inside the 96 slices
+    'edge': _edge(),
+    'edge_m2': _edge(n_mat=2), 'edge_m1': _edge(n_mat=1), 'edge_m5': _edge(n_mat=5), 'edge_m7': _edge(n_mat=7),
+    # 16 slices: rays enter and leave through the z faces; the steep rows pass far above and below the volume
+    'edge_thin': _edge(nz=16),
+    # the source above the top face (1.6 cm) of that volume, at the height from which the steepest row runs down through its
+    # centre; the rows centred on the source
+    'edge_above': _edge(nz=16, src_z=6.5, row_centre=6.5),
+    # views from atan2(dy, dx): the central ray sits on the dominant-axis switch of a grid with dx != dy != dz
+    'edge_aniso': _edge(dy=0.198, dz=0.25, nz=80, theta0=float(np.arctan2(0.198, 0.2))),
+    # every staged-column width of cone_cols_kernel (288, 544, 1056 bytes) and cone_rows_kernel (more than 1024 slices)
+    'edge288': _edge(nz=250, **_TALL), 'edge544': _edge(nz=500, **_TALL), 'edge1056': _edge(nz=1000, **_TALL),
+    'edge1040': _edge(nz=1040, **_TALL),
+    # a second chunk of 256 lanes with one live lane
+    'edge_r257': _edge(nx=11, ny=9, nz=64, n_views=4, n_ch=5, n_rows=257),
+    # 131 slabs on a diagonal of 0.05 cm voxels (the byte counters flush after 128); the source at the height from which the
+    # steepest row runs down through the centre of the volume
+    'edge_slabs': _edge(nx=131, ny=131, nz=144, n_ch=5, n_rows=9, dx=0.05, dy=0.05, dz=0.05, src_z=6.375, row_centre=6.375),
+    # inside the range no other scan reaches, off the rounding edge
+    'edge90': _edge(share=0.9),
+}
+SCANS.update(EDGE_SCANS)
+
+
+def cone_rays_f64(s):
+    """Per-ray figures of a cone scan in float64 / in the mirror's integers, [views][rows][channels] each: 'SW' (the slice
+    step per slab in 2^-40, as orc_cone_pathlen rounds it), 'past' (how many slices the ray's slice coordinate w0 + i sw runs
+    past the nearer z face over the plan's slab range; <= 0 inside, -inf for a ray without slabs) and 'ties' (slabs whose two
+    crossing fractions tv and tw, restated in float32 as dda_slab and orc_cone_pathlen form them, are equal and below 1)."""
+    from oracle import c_oracle as co
+    plan = co.plan(s.geom(co.make_geom), s.view_cs, s.chan_cs, 0, s.n_views).reshape(s.n_views, 1, s.n_ch)
+    cb, sb = s.view_cs[:, 0][:, None, None], s.view_cs[:, 1][:, None, None]
+    cg, sg = s.chan_cs[:, 0][None, None, :], s.chan_cs[:, 1][None, None, :]
+    sx, sy = s.sid * cb, s.sid * sb
+    ex, ey = -(cb * cg - sb * sg), -(sb * cg + cb * sg)
+    axis = (plan['flags'] & 1).astype(np.int64)
+    su = np.where(axis == 0, sx / s.dx + 0.5 * s.nx, sy / s.dy + 0.5 * s.ny)
+    eu = np.where(axis == 0, ex / s.dx, ey / s.dy)
+    ws = s.src_z / s.dz + 0.5 * s.nz
+    sw = ((s.row_z[None, :, None] - s.src_z) / s.dz) / (s.sdd * eu)
+    w0 = ws - su * sw
+    one = 2.0 ** 40
+    SW, W0 = np.rint(sw * one).astype(np.int64), np.rint(w0 * one).astype(np.int64)
+    i0, n = plan['i_first'].astype(np.int64), plan['n_slabs'].astype(np.int64)
+    wa, wb = w0 + i0 * sw, w0 + (i0 + n) * sw
+    past = np.maximum(np.maximum(-wa, -wb), np.maximum(wa, wb) - s.nz)
+    past = np.where(n > 0, past, -np.inf)
+    # the two crossing fractions of every slab (float32, operation for operation as the mirror)
+    with np.errstate(divide='ignore'):
+        kfw = (np.minimum(np.where(SW != 0, one / np.abs(SW.astype(F64)), 2.0 ** 24), 2.0 ** 24) * 2.0 ** -32).astype(F32)
+    wpos = np.where(SW > 0, 0xFFFFFFFF, 0).astype(np.uint32)
+    smask = np.where(plan['flags'] & 2, 0xFFFFFFFF, 0).astype(np.uint32)
+    ties = np.zeros(SW.shape, np.int64)
+    frac = lambda X, mask, k: np.minimum(((((X >> 8) & 0xFFFFFFFF).astype(np.uint32)) ^ mask).astype(F32) * k, F32(1.0))
+    for k in range(int(n.max(initial=0))):
+        i = i0 + k
+        tv = frac(plan['V0'] + i * plan['SV'], smask, plan['kf'])
+        tw = frac(W0 + i * SW, wpos, kfw)
+        ties += (k < n) & (tv == tw) & (tv < 1.0)
+    return dict(SW=SW, past=past, ties=ties)
+
 
 _scans = {}
 

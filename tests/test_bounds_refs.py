@@ -157,6 +157,98 @@ def test_tie_ray_cap_of_every_scan(name):
                 assert tie[vb:ve].mean() <= 0.02, (vb, ve)
 
 
+# ---- the cone scans at the edge of the slope contract (bounds_refs.EDGE_SCANS) --------------------------------------------------
+
+_edge_figures = {}
+
+
+def edge_figures(name):
+    """Both CPU references of an edge scan and what the tests below ask of it, computed once per scan."""
+    if name not in _edge_figures:
+        from oracle import c_oracle as co
+        s = br.scan(name)
+        g = s.geom(co.make_geom)
+        cone = lambda dda: co.project_cone(g, s.view_cs, s.chan_cs, 0, s.n_views, s.row_z, s.src_z, s.vol, s.mu, s.w, dda=dda, n_threads=8)
+        (cnt_m, pl_m), (cnt_c, pl_c) = cone(True), cone(False)
+        tie = br.tie_rays(s, 0, s.n_views)
+        live = ~np.broadcast_to(tie[:, None, :, None], pl_m.shape)
+        rays = br.cone_rays_f64(s)
+        fig = dict(tie=float(tie.mean()), pathlen=float(np.abs(pl_m.astype(F64) - pl_c)[live].max()),
+                   counts=br.counts_rel(cnt_m, cnt_c, tie), past=float(rays['past'].max()),
+                   sw=float(np.abs(rays['SW']).max() / 2.0 ** 40), ties=int(rays['ties'].sum()),
+                   n_slabs=int(co.plan(g, s.view_cs, s.chan_cs, 0, s.n_views)['n_slabs'].max()),
+                   material=(pl_c[..., 1:].sum(-1) if s.n_mat > 1 else pl_c[..., 0]) > 0.0)          # [views][rows][channels]
+        print(name, {k: (round(float(v.mean()), 3) if k == 'material' else v) for k, v in fig.items()})
+        _edge_figures[name] = fig
+    return _edge_figures[name]
+
+
+AT_THE_LIMIT = sorted(n for n in br.EDGE_SCANS if n != 'edge90')
+
+
+@pytest.mark.parametrize('name', sorted(br.EDGE_SCANS))
+def test_edge_scans_sit_on_the_slope_limit(name):
+    """max_abs_dz of every edge scan is the last float64 the restated cone_slope_ok accepts: the next one is refused (edge90:
+    0.9 of that value).  tests/test_gpu_bounds_projection.py shows the library draws the line at the same float64."""
+    s = br.scan(name)
+    limit = br.slope_limit(s.dx, s.dy, s.dz, s.sdd)
+    up = float(np.nextafter(limit, np.inf))
+    assert br.slope_ok(limit, s.dx, s.dy, s.dz, s.sdd) and not br.slope_ok(up, s.dx, s.dy, s.dz, s.sdd)
+    assert br.slope_ok(s.max_abs_dz, s.dx, s.dy, s.dz, s.sdd)
+    if name == 'edge90':
+        assert abs(s.max_abs_dz / limit - 0.9) < 1e-12
+    else:
+        assert s.max_abs_dz == limit
+        assert not br.slope_ok(float(np.nextafter(s.max_abs_dz, np.inf)), s.dx, s.dy, s.dz, s.sdd)
+
+
+@pytest.mark.parametrize('name', sorted(br.EDGE_SCANS))
+def test_edge_scan_mirror_against_float64_siddon(name):
+    """The two CPU references agree at the slope limit as they do far below it: no tie rays beyond the 2 % cap, per-material path
+    lengths of the mirror within 2e-6 cm of the float64 3-D Siddon on every other ray (3.5 x the worst of the CPU probes that
+    chose these scans, both sides references; chords up to 11.3 cm), counts within REL_TOL.  Measured (tie share 0 everywhere):
+                 path length [cm]  counts (rel)               path length [cm]  counts (rel)
+      edge         4.5e-7           5.7e-8       edge288       1.8e-7           6.3e-8
+      edge_m2      4.6e-7           1.1e-7       edge544       2.0e-7           7.7e-8
+      edge_m1      6.8e-7           1.4e-10      edge1056      2.0e-7           5.3e-8
+      edge_m5      3.2e-7           1.1e-7       edge1040      1.7e-7           8.1e-8
+      edge_m7      2.1e-7           8.2e-8       edge_r257     2.5e-7           9.1e-8
+      edge_thin    2.5e-7           1.0e-7       edge_slabs    5.1e-7           7.9e-8
+      edge_above   3.0e-7           1.1e-7       edge90        3.7e-7           5.5e-8
+      edge_aniso   4.1e-7           7.9e-8"""
+    from test_gpu_siddon import REL_TOL
+    fig = edge_figures(name)
+    assert fig['tie'] <= 0.02
+    assert fig['pathlen'] <= 2e-6, fig['pathlen']
+    assert fig['counts'] < REL_TOL, fig['counts']
+
+
+def test_edge_scans_reach_what_they_claim():
+    """The figures that make the edge scans worth their run.  Measured:
+      edge        every ray crosses material (the two outermost rows included); 34 slabs with tv == tw < 1 in float32
+      edge_thin   29 % of the rays cross material; a ray's slice coordinate runs 33.4 slices past a z face
+      edge_above  18 % cross material; 65.9 slices past a z face
+      edge_slabs  131 slabs on the longest ray (its chord: 11.3 cm)
+      max |SW| / 2^40: 1.000000 for every scan at the limit but edge_aniso (0.995013: dy = 0.99 dx), 0.9 for edge90"""
+    edge = edge_figures('edge')
+    assert edge['material'].mean() >= 0.9 and edge['material'][:, [0, -1]].all()
+    assert edge['ties'] >= 1
+    for name in ('edge_thin', 'edge_above'):
+        fig = edge_figures(name)
+        assert fig['past'] > 16.0 and fig['material'].mean() >= 0.1, name
+    assert edge_figures('edge_slabs')['n_slabs'] > 128
+    for name in AT_THE_LIMIT:
+        assert edge_figures(name)['sw'] >= 0.99, name
+    assert 0.89 < edge_figures('edge90')['sw'] <= 0.9
+
+
+def test_row_centre_moves_the_rows_only():
+    """Scan(row_centre=c): the same rows, centred on c; without it the scan is what it was."""
+    a, b = br.Scan(**br.SCANS['cone']), br.Scan(**dict(br.SCANS['cone'], row_centre=0.25))
+    assert np.array_equal(b.row_z, a.row_z + 0.25) and np.array_equal(a.row_z, (np.arange(10) - 4.5) * 0.8)
+    assert np.array_equal(a.vol, b.vol) and np.array_equal(a.mu, b.mu) and np.array_equal(a.w, b.w)
+
+
 def test_counts_comparison_rejects_a_wrong_ray():
     from oracle import c_oracle as co
     s = br.scan('r4')

@@ -54,6 +54,18 @@ Kernel (__global__) -> test that launches it
                  cone_cols_kernel<.., 8, ..>              test_switches (DEXCT_CONE_KB=8)
                  cone_rows_kernel<1>, <2>, <3, 4>         test_cone[rows, nz 1040], test_switches (DEXCT_CONE_COLS=0)
                  cone_rows_kernel<3, 2>, <3, 8>, <3, 4, false>   test_switches (DEXCT_CONE_BATCH, DEXCT_CONE_LDSC)
+                 every cone kernel with max_abs_dz the LAST float64 cone_slope_ok accepts (bounds_refs.EDGE_SCANS; the next one is
+                 refused: test_refused_calls_launch_nothing) - one slice per slab on the diagonals of isotropic voxels:
+                 cone_kernel<1|2|3> and <0> (5 ids)       test_cone_at_the_slope_limit[cone-edge, edge_m1, edge_m2, edge_m5, ..]
+                 cone_cols_kernel<1|2|3, 4, 288>          [cone_rows-edge_m1, edge_m2, edge, edge_thin, edge_above (slices clamped
+                                                          up to 66 past a z face), edge_aniso, edge288, edge_r257 (2 chunks of lanes),
+                                                          edge_slabs (131 slabs: a flush of the byte counters), edge90]
+                 cone_cols_kernel<3, 4, 544|1056>         [cone_rows-edge544, edge1056]
+                 cone_rows_kernel<3, 4>                   [cone_rows-edge1040]
+                 the group passes of all of these         [cone_grouped-*]: edge_m5 and edge_m7 take two and three passes
+                 with the sample                          test_sample_at_the_slope_limit
+                 cone_rows_kernel<3, 2|4|8, LDSC or not>, cone_cols_kernel<3, 8, 288|544>, a view tile of 3:
+                                                          test_switches_at_the_slope_limit (the bits of the default form)
   detect.hip     detect_kernel<2..48, RMAX> / <.., 1>     test_material_counts (layout 1 with 8 rows: RMAX rays per thread; layout 0: one)
                  detect_kernel_chunked                    test_material_counts (49, 200; 1 through dexct_cone_project_grouped)
                  detect_kernel with 1, 3, 4 spectra, the sample of a view sub-range: test_three_and_four_spectra,
@@ -77,6 +89,19 @@ within 2.7e-7 of the float64 Siddon (bound 1e-5).  Reconstruction, worst |err| /
 filter 0.14, back-projection 0.13, FDK 0.05 - the derivations of tests/bounds_refs.py stand as written.  The refused-call
 cases of dexct_cone_project_grouped pass with the fix above (the defect was found by reading; the unfixed library was not
 run).  The issue's "66 rows of nz 80 from z_first 16" cannot be run (16 + 66 > 80: DEXCT_EINVAL); scan r66 has nz = 96.
+
+The edge of the slope contract (test_cone_at_the_slope_limit, test_sample_at_the_slope_limit, test_switches_at_the_slope_limit,
+the three max_dz = nextafter cases of test_refused_calls_launch_nothing).  Record of the run on an MI355X: these 73 cases take
+2.5 s run alone, interpreter and library start included (this module's 470 cases 6.0 s; the 9 new cases of
+tests/test_gpu_siddon.py 2.1 s alone; the whole -m gpu suite 332 s).  Nothing failed on the way and no kernel changed.  Per entry
+point, over all its edge scans:
+  dexct_cone_project          path lengths bit-equal to the mirror on all rays; counts within 2.15e-7 of the float64 Siddon (edge_m2)
+  dexct_cone_project_rows     path lengths bit-equal on all rays; counts within 2.15e-7 (edge_m2); every A/B form the bits of the default
+  dexct_cone_project_grouped  path lengths bit-equal on all rays; counts within 2.18e-7 (edge_m2)
+No guard changed, no output depended on a fill, dexct_last_hip_error() stayed 0, every output element was written - with slice
+indices up to 66 slices past a z face (edge_above), 248 past on rays that miss (edge_slabs) - and the library refuses exactly the
+float64 after the one scan edge runs at.  Through Projector (test_random_cone_beam_scans_near_the_slope_limit, 0.906 - 0.998 of
+the limit): path lengths bit-equal, counts within 7.4e-7.
 """
 import ctypes as C
 
@@ -574,6 +599,55 @@ def test_cone_rays_that_miss(hip, entry, name):
     sampled_equals_add_noise(hip, name, entry, pathlen=False, log=True, vb=2, ve=5)
 
 
+# ---- the cone kernels at the edge of the slope contract: max_abs_dz is the last float64 dexct accepts (bounds_refs.EDGE_SCANS)
+
+EDGE_CONE = ['edge', 'edge_m2', 'edge_m1', 'edge_m5', 'edge_thin', 'edge_above', 'edge_aniso', 'edge_slabs', 'edge90']
+EDGE_CASES = ([('cone', n) for n in EDGE_CONE] + [('cone_rows', n) for n, kw in br.EDGE_SCANS.items() if kw.get('n_mat', 3) <= 3]
+              + [('cone_grouped', n) for n in br.EDGE_SCANS])
+
+
+@pytest.mark.parametrize('entry,name', EDGE_CASES)
+def test_cone_at_the_slope_limit(hip, entry, name):
+    """Every ray of every edge scan: three-piece slabs with tv == tw ties (edge*), slice indices tens of slices past either z face
+    under the clamp of the row kernels (edge_thin, edge_above, edge_slabs), every staged-column width and cone_rows_kernel
+    (edge288 .. edge1040), a second chunk of lanes (edge_r257), a flush of the byte counters inside a steep ray (edge_slabs),
+    1 / 2 / 3 materials and two and three group passes (edge_m*).  With path lengths and the log, then with the variance."""
+    project(hip, name, entry, pathlen=True, log=True)
+    project(hip, name, entry, pathlen=False, var=True)
+
+
+@pytest.mark.parametrize('entry', CONE_ENTRIES)
+@pytest.mark.parametrize('name', ['edge', 'edge_thin'])
+def test_sample_at_the_slope_limit(hip, entry, name):
+    sampled_equals_add_noise(hip, name, entry, pathlen=False, log=True)
+
+
+CONE_KNOBS = ('DEXCT_CONE_COLS', 'DEXCT_CONE_KB', 'DEXCT_CONE_BATCH', 'DEXCT_CONE_LDSC', 'DEXCT_CONE_VIEW_TILE')
+# (DEXCT_CONE_BATCH and DEXCT_CONE_LDSC act on cone_rows_kernel: on these scans together with DEXCT_CONE_COLS=0, on edge1040 alone)
+EDGE_FORMS = [dict(DEXCT_CONE_COLS='0'), dict(DEXCT_CONE_KB='8'), dict(DEXCT_CONE_BATCH='2'), dict(DEXCT_CONE_BATCH='8'),
+              dict(DEXCT_CONE_LDSC='0'), dict(DEXCT_CONE_VIEW_TILE='3'), dict(DEXCT_CONE_COLS='0', DEXCT_CONE_BATCH='2'),
+              dict(DEXCT_CONE_COLS='0', DEXCT_CONE_BATCH='8'), dict(DEXCT_CONE_COLS='0', DEXCT_CONE_LDSC='0')]
+EDGE_SWITCHES = ([('cone_rows', n, env) for n in ('edge', 'edge544') for env in EDGE_FORMS]
+                 + [('cone_rows', 'edge1040', env) for env in EDGE_FORMS[2:5]] + [('cone_grouped', 'edge_m7', EDGE_FORMS[0])]
+                 # cone_rows_kernel's own clamp of the slice index, 33 and 66 slices past a z face
+                 + [('cone_rows', n, EDGE_FORMS[0]) for n in ('edge_thin', 'edge_above')])
+_default_form = {}
+
+
+@pytest.mark.parametrize('entry,name,env', EDGE_SWITCHES, ids=[f'{e}-{n}-{"-".join(f"{k}={v}" for k, v in env.items())}' for e, n, env in EDGE_SWITCHES])
+def test_switches_at_the_slope_limit(hip, monkeypatch, entry, name, env):
+    """The A/B launch forms on steep rays: guarded like every case, and the bits of the default form in every output."""
+    for k in CONE_KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    if (entry, name) not in _default_form:
+        _default_form[entry, name] = project(hip, name, entry, pathlen=True, log=True)['raw']
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    got = project(hip, name, entry, pathlen=True, log=True)['raw']
+    for n, a in _default_form[entry, name].items():
+        assert np.array_equal(got[n].view(np.int32), a.view(np.int32)), (n, env)
+
+
 SWITCHES = [('project', 'r66', dict(kernel=3), 'DEXCT_VIEW_TILE', '2'), ('packed', 'r16', {}, 'DEXCT_P16_STAGED', '0'),
             ('packed', 'r16', {}, 'DEXCT_DET_MASKS', '0'), ('packed', 'r16', {}, 'DEXCT_P16_MINW', '5'),
             ('packed', 'r16', {}, 'DEXCT_P16_MINW', '6'), ('packed', 'r16', {}, 'DEXCT_P16_MINW', '8'),
@@ -664,6 +738,10 @@ REFUSED = [
     ('cone', 'cone', dict(max_dz=1e4), ERANGE),                                   # too steep a cone
     ('cone_rows', 'cone', dict(max_dz=1e4), ERANGE),
     ('cone_grouped', 'cm7', dict(max_dz=1e4), ERANGE),
+    # the float64 after the last accepted one (scan edge runs AT that one in test_cone_at_the_slope_limit)
+    ('cone', 'edge', dict(max_dz=float(np.nextafter(scan('edge').max_abs_dz, np.inf))), ERANGE),
+    ('cone_rows', 'edge', dict(max_dz=float(np.nextafter(scan('edge').max_abs_dz, np.inf))), ERANGE),
+    ('cone_grouped', 'edge', dict(max_dz=float(np.nextafter(scan('edge').max_abs_dz, np.inf))), ERANGE),
     ('cone_rows', 'cm4', dict(), ERANGE),                                         # more than 3 materials on the row kernels
     ('cone', 'cone', dict(w2=True), EINVAL),
     ('cone_rows', 'cone', dict(w2=True), EINVAL),

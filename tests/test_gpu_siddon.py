@@ -500,6 +500,98 @@ def test_random_cone_beam_scans(hip, seed):
         assert rel.max() < REL_TOL, (seed, kernel, rel.max())
 
 
+def slope_share_of(max_dz, sdd, ph):
+    """The left-hand side of the library's slope contract (proj::cone_slope_ok: at most 1), its operations in its order."""
+    return max_dz / sdd / ph.dz * max(ph.dx, ph.dy) * 1.4142135623730951
+
+
+def slope_share(cone, ph):
+    return slope_share_of(float(np.max(np.abs(cone.row_z() - cone.src_z))), cone.SDD, ph)
+
+
+@pytest.mark.parametrize('seed', range(8))
+def test_random_cone_beam_scans_near_the_slope_limit(hip, seed):
+    """test_random_cone_beam_scans between 0.9 and 1.0 of the steepest cone the library accepts (the scans above stay below
+    0.6): nearly every slab of a diagonal ray has a z crossing.  Seeds 0 and 1: isotropic voxels and a first view at exactly
+    pi/4; odd seeds: a volume so thin that the outer rows leave through a z face, even seeds: one that holds every ray.  Path
+    lengths of kernels 1 and 2 equal the oracle's mirror bit for bit, counts agree with the float64 3-D textbook Siddon; more
+    than 3 ids go through the group passes, asked for (kernel 2) and picked by the default route (32 rows and more).
+    Record of the run on an MI355X: the 8 seeds (0.906 .. 0.998 of the limit) and the refusal below take 2.1 s together, start-up
+    included; counts within 7.4e-7."""
+    import dex_ct_sim_amd as dx
+    from dex_ct_sim_amd import forward_project as fp
+    from dex_ct_sim_amd.system import AIR, BONE, WATER, Material
+    rng = np.random.default_rng(7000 + seed)
+    nx, ny = int(rng.integers(9, 40)), int(rng.integers(9, 40))
+    dxv, dyv, dzv = (float(v) for v in rng.uniform(0.08, 0.4, 3))
+    if seed < 2:
+        dyv = dzv = dxv
+    half_diag = 0.5 * np.hypot(nx * dxv, ny * dyv)
+    sid = float(half_diag * rng.uniform(1.3, 2.5))
+    sdd = float(sid + half_diag * rng.uniform(1.0, 3.0))
+    n_mat = int(rng.integers(2, 7))
+    n_rows = int(rng.integers(32, 40)) if n_mat > 3 else int(rng.integers(2, 24))
+    n_views, n_ch = int(rng.integers(3, 12)), int(rng.integers(5, 40))
+    limit = sdd * dzv / (max(dxv, dyv) * np.sqrt(2.0))
+    reach = float(rng.uniform(0.9, 1.0)) * limit
+    src_z = float(rng.uniform(-0.3, 0.3) * reach)
+    h_iso = float((reach - abs(src_z)) / (0.5 * (n_rows - 1)) * sid / sdd)        # the outermost row AT reach
+    # slices from the centre that hold every ray: the far side of the grid at the steepest slope
+    inside = int(np.ceil((abs(src_z) + reach * (sid + half_diag) / sdd) / dzv)) + 1
+    nz = int(rng.integers(2, max(3, inside // 4))) if seed % 2 else 2 * inside
+    vol = rng.integers(0, n_mat, (nz, ny, nx), dtype=np.uint8)
+    vol[rng.random(vol.shape) < 0.4] = 0
+    mats = ([AIR, WATER, BONE] + [Material(f'm{i}', 1.0 + 0.2 * i, 'H(11.2)O(88.8)') for i in range(3, n_mat)])[:n_mat]
+    ph = dx.VoxelPhantom.from_array('rnd', vol, mats, dx=dxv, dy=dyv, dz=dzv)
+    cone = dx.FanBeamGeometry(N_channels=n_ch, N_proj=n_views, gamma_fan=float(rng.uniform(0.2, 1.6)), SID=sid, SDD=sdd,
+                              h_iso=h_iso, N_rows=n_rows, cone=True, src_z=src_z)
+    if seed < 2:
+        cone.thetas = cone.thetas + np.pi / 4
+    assert 0.9 - 1e-9 <= slope_share(cone, ph) <= 1.0, slope_share(cone, ph)
+    g = co.make_geom(n_views, n_ch, n_rows, 0, nx, ny, nz, dxv, dyv, dzv, sid, sdd)
+    sp = spectra()
+    E, mu, w = fp.merged_tables(cone, ph, sp)
+    _, rpl = co.project_cone(g, cone.view_cs(), cone.chan_cs(), 0, n_views, cone.row_z(), src_z, vol, mu, w, dda=True,
+                             n_threads=8)
+    cls, _ = co.project_cone(g, cone.view_cs(), cone.chan_cs(), 0, n_views, cone.row_z(), src_z, vol, mu, w, dda=False,
+                             n_threads=8)
+    tie = on_plane_rays(g, cone, n_views)[:, None, :].repeat(n_rows, 1)
+    for kernel in ((1, 2) if n_mat <= 3 else (1, 2, 0)):
+        pj = projector(cone, ph, kernel=kernel)
+        assert pj.n_mat == n_mat
+        assert pj.cone_groups == (kernel != 1 and n_mat > 3), (seed, kernel)
+        (counts, pl), _ = pj.project(sp, want_pathlen=True)
+        assert np.array_equal(pl.cpu().numpy(), rpl), (seed, kernel)
+        rel = np.abs(counts.cpu().numpy() - cls) / cls
+        rel[:, tie] = 0.0
+        print(seed, kernel, 'f', slope_share(cone, ph), 'nz', nz, 'rows', n_rows, 'ids', n_mat, 'counts rel', rel.max())
+        assert rel.max() < REL_TOL, (seed, kernel, rel.max())
+
+
+def test_cone_one_float64_past_the_slope_limit_is_refused(hip):
+    """The last float64 the slope contract accepts projects; the next one raises, as a cone 30 times too steep does
+    (test_cone_beam_matches_oracle)."""
+    import dex_ct_sim_amd as dx
+    from dex_ct_sim_amd._native import DexctError
+    _, ph = small_scan(n=24, nz=8, n_views=4, n_channels=16, n_rows=8)
+    sid, sdd = 60.0, 100.0
+    limit = sdd * ph.dz / (max(ph.dx, ph.dy) * 1.4142135623730951)
+    while slope_share_of(limit, sdd, ph) > 1.0:
+        limit = float(np.nextafter(limit, -np.inf))
+    while slope_share_of(float(np.nextafter(limit, np.inf)), sdd, ph) <= 1.0:
+        limit = float(np.nextafter(limit, np.inf))
+    sp = spectra()
+    for max_dz, accepted in ((limit, True), (float(np.nextafter(limit, np.inf)), False)):
+        cone = dx.FanBeamGeometry(N_channels=16, N_proj=4, SID=sid, SDD=sdd, h_iso=1.0, N_rows=3, cone=True)
+        cone.row_z = lambda m=max_dz: np.array([-m, 0.0, m])                 # (three rows: -m and m exactly)
+        assert (slope_share(cone, ph) <= 1.0) == accepted
+        if accepted:
+            projector(cone, ph).project(sp)
+        else:
+            with pytest.raises(DexctError):
+                projector(cone, ph).project(sp)
+
+
 @pytest.mark.parametrize('nz,n_rows', [(300, 300), (520, 40), (130, 257), (1030, 12)])
 def test_cone_row_kernels_on_tall_volumes(hip, nz, n_rows, monkeypatch):
     """The row-parallel cone kernels on volumes and detectors the random scans above do not reach: columns of more

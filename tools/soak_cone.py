@@ -8,7 +8,10 @@ materials, dense random volumes or small objects in air.  Demanded in every case
   * (round 6) with more, the group passes of the row-parallel kernels: path lengths bit-identical, counts identical for 5 - 48
     table rows; the noisy sample of the host's choice = dexct_add_noise on the same call's signal and variance.
 
-    python tools/soak_cone.py [n_cases] [first_seed]
+    python tools/soak_cone.py [n_cases] [first_seed] [share]
+
+``share``: how far the outermost row reaches towards the steepest cone the library accepts (proj::cone_slope_ok), as one number
+(default 0.6) or as a range ``lo:hi`` drawn from per case, e.g. ``0.9:1.0``.
 """
 import os
 import sys
@@ -27,6 +30,10 @@ from oracle import c_oracle as co
 
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+share_lo, _, share_hi = (sys.argv[3] if len(sys.argv) > 3 else '0.6').partition(':')
+share_lo, share_hi = float(share_lo), float(share_hi or share_lo)
+if not 0.0 < share_lo <= share_hi <= 1.0:
+    sys.exit('share: one number or lo:hi within (0, 1]')
 dev = torch.device('cuda:0')
 t0 = time.time()
 fails, rays, n_rows_kernel, n_groups = 0, 0, 0, 0
@@ -41,7 +48,9 @@ for case in range(n_cases):
     n_rows = int(rng.choice([1, 2, 7, 24, 31, 32, 33, 64, 100, 256, 300]))
     n_views, n_ch = int(rng.integers(1, 8)), int(rng.integers(1, 120))
     # the kernels take at most one z-plane per dominant-axis slab: |dz/du| <= 1 for every ray
-    reach = 0.6 * sdd * dzv / (max(dxv, dyv) * np.sqrt(2.0))
+    # (a range is drawn from a generator of its own: the cases themselves stay those of the default share)
+    share = share_lo if share_hi == share_lo else float(np.random.default_rng(990000 + seed).uniform(share_lo, share_hi))
+    reach = share * sdd * dzv / (max(dxv, dyv) * np.sqrt(2.0))
     src_z = float(rng.uniform(-0.3, 0.3) * reach)
     half_rows = max(0.5 * (n_rows - 1), 0.5)
     h_iso = float((reach - abs(src_z)) / half_rows * sid / sdd * rng.uniform(0.05, 1.0))
