@@ -57,7 +57,9 @@ struct PackedArgs {
   int view_tile;
   int det_masks;           // skip detection FMAs of spectrum slots with zero weights (blocks of four energies)
   int det_absent;          // detect waves whose rays all miss the last material without it (DEXCT_DET_ABSENT=0: off)
-  int staged_store;        // store the results of a wave through LDS as whole lines (DEXCT_P16_STAGED=0: per-round 16-B stores)
+  // the staged noise-free forms detect each distinct quad of rows once per wave (siddon_packed.hip, dedup_index.h;
+  // DEXCT_DET_DEDUP=0: every quad is detected).  (The word held DEXCT_P16_STAGED, which only the host reads: P16Launch::staged_store.)
+  int det_dedup;
   // quantum noise (the NOISY instantiations; ABI 6): the kernel detects the variance with the counts and, `sample` != 0, draws
   // the sample itself (noise_sample.h; the Philox counter needs the GLOBAL view)
   int view_begin;

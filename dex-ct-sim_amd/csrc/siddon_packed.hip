@@ -27,6 +27,7 @@
 // the kernel (dexct_siddon_project_packed_skip) enter no slab in their lists whose pieces all lie in marked columns: the sweeps
 // get shorter, every sum keeps its bits (profiles/rows16_air_skip.md).
 #include "common.h"
+#include "dedup_index.h"
 #include "noise_sample.h"
 #include "proj_host.h"
 #include "sliced_count.h"
@@ -40,6 +41,19 @@ constexpr int kCrossTrip = 8;       // crossing slabs per trip of theirs (Sliced
 constexpr int kAirBatch = 2;         // classification iterations whose air-map lookups fly together (kP16Super / 64 = 2 at least)
 static_assert(kP16Super % (kAirBatch * 64) == 0, "whole batches for every lane group");
 static_assert(kP16Super % kFullTrip == 0 && kP16Super % kCrossTrip == 0, "the lists are padded to whole trips inside their LDS");
+// LDS of a wave (= workgroup) that carries n_pairs pairs: their lists, and at least the staged store of the results (64 bytes per
+// lane and spectrum), which reuses the lists' space
+__host__ __device__ constexpr int p16_lds_bytes(int n_pairs) {
+  const int lists = n_pairs * kP16Super * (int)(sizeof(CrossRec) + sizeof(uint32_t));
+  return lists < 2 * 64 * 64 ? 2 * 64 * 64 : lists;
+}
+// what the list of distinct quads (dedup_index.h) keeps behind itself, in the last bytes of the wave's LDS - not in registers:
+// the detection rounds have none to spare
+struct DedupTail {
+  float2 chord[4];       // (chord_u, len_per_u) of the wave's pairs
+  int pair_end[4];       // [k], k < 3: entries of the pairs 0..k (an entry finds its pair by counting); [3]: entries in all
+  uint32_t src[64];      // per lane, 8 bits per quad: the entry whose results the quad takes (< 192)
+};
 
 // GROUPED: a material-group pass (ids = codes 0..3 of one group of three materials): raw accumulators (units of u) go to
 // acc_out[(mat_base + code) * n_rays + ray], no detection (dexct_siddon_project_grouped_packed).
@@ -312,13 +326,134 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
     }
     return;
   }
+  // ---- Distinct quads (the staged noise-free forms; pa.det_dedup).  The counts of a ray are a function of its sums and of its
+  // pair's chord, and in a stacked fan the rows of a pair cross the same slabs: rows whose columns carry the same ids along the
+  // ray have bitwise equal sums (an extruded part of the object, the water above and below an insert).  A quad = a lane's four
+  // rows of one round; it is FRESH when a sum differs bitwise from the same row of the quad before it in the pair (the same
+  // lane's round before, for round 0 the last round of the lane below; a pair's first quad always is).  The fresh quads go to a
+  // list in LDS (the slab lists are dead: the space the staged store reuses too), lane j of round k detects entry 64 k + j and
+  // writes the results over it, and every quad then takes the results of the last fresh quad at or before it into the stage.
+  // Where the list saves no round (dedup::use_list: wave-uniform) the rounds run on the rows as they always did.
+  // (Not in the two-material form without the air-column map: it fits the 96 VGPRs of a fifth wave per SIMD, and with the list
+  // in it it took 99, or 96 with 3 of them spilled to scratch; its SKIP form runs four waves either way and has the list.)
+  constexpr bool kDedup = STAGED && !NOISY && !GROUPED && !(NM == 2 && !SKIP);
+  constexpr int kEntry = dedup::entry_bytes(NM);
+  int list_rounds = 0;                       // > 0: the wave detects its list, in so many rounds
+  auto dedup_tail = [&]() { return reinterpret_cast<DedupTail*>(reinterpret_cast<uint8_t*>(lds_lists) + p16_lds_bytes(n_pairs) - sizeof(DedupTail)); };
+  float chord_u = p.chord_u, len_per_u = p.len_per_u;
+  if constexpr (kDedup) {
+    if (pa.det_dedup) {
+      // (lpp is a power of two; the lane's place in its pair is taken from the lane, not kept from the traversal)
+      const bool pair_first = (lane & (lpp - 1)) == 0;
+      int live_rounds = 0, n_fresh = 0, below = 0;        // below: fresh quads (of all rounds) in the lanes below this one
+      uint32_t own = 0;                                    // bit q: quad (lane, q) is fresh
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        bool diff = q == 0 && pair_first;
+#pragma unroll
+        for (int m = 0; m < NM - 1; ++m)
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            const uint32_t mine = __float_as_uint(corr[m][4 * q + rr]);
+            // (every lane takes part in the shuffle; lane 0 reads itself and is the first of its pair)
+            const uint32_t prev = q == 0 ? (uint32_t)__shfl_up((int)__float_as_uint(corr[m][12 + rr]), 1) : __float_as_uint(corr[m][4 * q - 4 + rr]);
+            diff |= mine != prev;
+          }
+        const bool live_q = lane_live && r0 + 4 * q < a.g.n_rows;
+        const unsigned long long fresh_q = __ballot(diff && live_q);
+        own |= (diff && live_q) ? 1u << q : 0u;
+        below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(fresh_q >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fresh_q, (uint32_t)below));
+        n_fresh += __popcll(fresh_q);
+        live_rounds += __ballot(live_q) != 0ull ? 1 : 0;
+      }
+      if (dedup::use_list(n_fresh, live_rounds, NM, p16_lds_bytes(n_pairs), (int)sizeof(DedupTail))) {
+        list_rounds = dedup::list_rounds(n_fresh);
+        if (a.pathlen) {             // (test output) per ray, as the rounds write it: the rows go once round the register array
+#pragma unroll 1
+          for (int q4 = 0; q4 < 4; ++q4) {
+#pragma unroll
+            for (int rr = 0; rr < 4; ++rr) {
+              const int r = r0 + 4 * q4 + rr;
+              float others = 0.0f;
+#pragma unroll
+              for (int m = 1; m < NM; ++m) others += corr[m - 1][rr];
+              if (lane_live && r < a.g.n_rows) {
+                float* pl = a.pathlen + ray_index(a, v, r, c) * NM;
+                pl[0] = (p.chord_u - others) * p.len_per_u;
+#pragma unroll
+                for (int m = 1; m < NM; ++m) pl[m] = corr[m - 1][rr] * p.len_per_u;
+              }
+            }
+#pragma unroll
+            for (int m = 0; m < NM - 1; ++m) {
+              float first[4];
+#pragma unroll
+              for (int rr = 0; rr < 4; ++rr) first[rr] = corr[m][rr];
+#pragma unroll
+              for (int row = 0; row < 12; ++row) corr[m][row] = corr[m][row + 4];
+#pragma unroll
+              for (int rr = 0; rr < 4; ++rr) corr[m][12 + rr] = first[rr];
+            }
+          }
+        }
+        uint8_t* entries = reinterpret_cast<uint8_t*>(lds_lists);
+        DedupTail* tail = dedup_tail();
+        uint32_t src_entry = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int e = dedup::prefix_from_counts(below, own, q) - 1;
+          src_entry |= ((uint32_t)e & 0xFFu) << (8 * q);
+          if ((own >> q) & 1u) {
+#pragma unroll
+            for (int m = 0; m < NM - 1; ++m)
+              *reinterpret_cast<float4*>(entries + e * kEntry + m * 16) =
+                  make_float4(corr[m][4 * q], corr[m][4 * q + 1], corr[m][4 * q + 2], corr[m][4 * q + 3]);
+          }
+        }
+        tail->src[lane] = src_entry;
+        // the entries of a pair end where those of the next pair begin: what lies below that pair's first lane (the last pair's,
+        // and the unused ones', at the end of the list; the stores of a wave land in program order)
+        const int pair = lane >> __builtin_ctz((unsigned)lpp);
+        if (lane < 4) tail->pair_end[lane] = n_fresh;
+        if (pair_first) {
+          tail->chord[pair] = make_float2(p.chord_u, p.len_per_u);
+          if (pair > 0) tail->pair_end[pair - 1] = below;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+      }
+    }
+  }
   AirCache air_cache{0.0f, {0.0f, 0.0f}, false, {0.0f, 0.0f}};
   const size_t sstride_n = (size_t)a.n_local_views * a.g.n_rows * a.g.n_channels;
+  const bool use_list = kDedup && list_rounds > 0;
 #pragma unroll 1
-  for (int q4 = 0; q4 < 4; ++q4) {
+  for (int q4 = 0; q4 < (use_list ? list_rounds : 4); ++q4) {
     const bool round_live = lane_live && r0 + 4 * q4 < a.g.n_rows;
     if (!staged && !round_live) break;
-    if (staged && __ballot(round_live) == 0ull) break;          // wave-uniform: nobody has rows left
+    if (staged && !use_list && __ballot(round_live) == 0ull) break;          // wave-uniform: nobody has rows left
+    const int entry = 64 * q4 + lane;          // (list rounds)
+    bool entry_live = false;
+    if constexpr (kDedup) {
+      if (use_list) {      // this round's rows are the entry's; lanes past the end of the list detect air, which disturbs no wave-wide short cut
+        const uint8_t* entries = reinterpret_cast<const uint8_t*>(lds_lists);
+        const DedupTail* tail = dedup_tail();
+        const int pair_end[4] = {tail->pair_end[0], tail->pair_end[1], tail->pair_end[2], tail->pair_end[3]};
+        entry_live = entry < pair_end[3];
+        const float2 cl = tail->chord[entry_live ? dedup::entry_pair(entry, pair_end, n_pairs) : 0];
+        chord_u = cl.x;
+        len_per_u = cl.y;
+#pragma unroll
+        for (int m = 0; m < NM - 1; ++m) {
+          float4 x = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+          if (entry_live) x = *reinterpret_cast<const float4*>(entries + entry * kEntry + m * 16);
+          corr[m][0] = x.x;
+          corr[m][1] = x.y;
+          corr[m][2] = x.z;
+          corr[m][3] = x.w;
+        }
+      }
+    }
     float res[2][4];
     {
       float L[4][NM];
@@ -332,12 +467,12 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
         float others = 0.0f;
 #pragma unroll
         for (int m = 1; m < NM; ++m) others += corr[m - 1][rr];
-        L[rr][0] = (p.chord_u - others) * p.len_per_u;
+        L[rr][0] = (chord_u - others) * len_per_u;
 #pragma unroll
-        for (int m = 1; m < NM; ++m) L[rr][m] = corr[m - 1][rr] * p.len_per_u;
+        for (int m = 1; m < NM; ++m) L[rr][m] = corr[m - 1][rr] * len_per_u;
       }
       if constexpr (staged || NOISY) {
-        if (a.pathlen) {             // (test output) written here so that the detection holds no store addresses
+        if (a.pathlen && !use_list) {             // (test output) written here so that the detection holds no store addresses
 #pragma unroll
           for (int rr = 0; rr < 4; ++rr)
             if (valid[rr] && round_live) {
@@ -399,7 +534,13 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
     // STAGED: the round's results go to LDS right away (plane s, float index 16 lane + row): no registers are held for
     // them, and the (corr[0][row], corr[1][row]) register pairs of the traversal's v_pk_add_f32 stay undisturbed
     if constexpr (staged) {
-      if (round_live) {
+      if (kDedup && use_list) {      // list rounds: the results replace the entry
+        if (entry_live) {
+          float4* e_w = reinterpret_cast<float4*>(reinterpret_cast<uint8_t*>(lds_lists) + entry * kEntry);
+          e_w[0] = make_float4(res[0][0], res[0][1], res[0][2], res[0][3]);
+          e_w[1] = make_float4(res[1][0], res[1][1], res[1][2], res[1][3]);
+        }
+      } else if (round_live) {
         float* stage_w = reinterpret_cast<float*>(lds_lists) + lane * 16 + 4 * q4;
 #pragma unroll
         for (int s = 0; s < kResSlots; ++s)
@@ -413,6 +554,34 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
       for (int row = 0; row < 12; ++row) corr[m][row] = corr[m][row + 4];
   }
   if constexpr (!staged) return;
+  if constexpr (kDedup) {
+    if (use_list) {      // every quad takes its entry's results (all reads, then all writes: the stage lies over the list)
+      const uint8_t* entries = reinterpret_cast<const uint8_t*>(lds_lists);
+      float4 got[4][2];
+      const uint32_t src_entry = dedup_tail()->src[lane];
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float4* e_r = reinterpret_cast<const float4*>(entries + ((src_entry >> (8 * q)) & 0xFFu) * kEntry);
+        got[q][0] = got[q][1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (lane_live && r0 + 4 * q < a.g.n_rows) {      // (a quad without rows has no entry to look at)
+          got[q][0] = e_r[0];
+          got[q][1] = e_r[1];
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+      __builtin_amdgcn_wave_barrier();
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (lane_live && r0 + 4 * q < a.g.n_rows) {
+          float4* stage_w = reinterpret_cast<float4*>(lds_lists) + lane * 4 + q;
+          stage_w[0] = got[q][0];
+          stage_w[256] = got[q][1];
+        }
+      }
+    }
+  }
   // ---- whole-line stores: the rounds left the 16 results of lane l and spectrum s in LDS at plane s, float index
   // 16 l + row; store instruction k takes the 16-byte piece 64 k + lane = (lane l' = piece / 4, rows 4 (piece % 4) ...):
   // consecutive lanes write consecutive 16 bytes
@@ -507,6 +676,7 @@ struct P16Launch {
   dim3 grid;
   size_t lds;
   hipStream_t st;
+  bool staged_store;      // DEXCT_P16_STAGED: store the results of a wave through LDS as whole lines (0: per-round 16-B stores)
 };
 template <int NM, int MINW, bool GROUPED, bool STAGED, bool NOISY, bool SKIP = false>
 static int launch_p16(const P16Launch& l) {
@@ -534,13 +704,12 @@ static int packed_shape(const dexct_fan_geom* geom, int32_t view_begin, int32_t 
   pa.view_tile = proj::read_knob(proj::knob::kViewTileP16);
   pa.det_masks = proj::read_knob(proj::knob::kDetMasks) != 0;
   pa.det_absent = proj::read_knob(proj::knob::kDetAbsent) != 0;
-  pa.staged_store = proj::read_knob(proj::knob::kP16Staged) != 0;
+  pa.det_dedup = proj::read_knob(proj::knob::kDetDedup) != 0;
   pa.view_begin = view_begin;
   const int n_pairs = 64 / pa.lanes_per_pair;
   if (!proj::grid_1d((size_t)(view_end - view_begin) * ((geom->n_channels + n_pairs - 1) / n_pairs) * pa.n_zchunks, grid))
     return DEXCT_ERANGE;
-  lds = (size_t)n_pairs * kP16Super * (sizeof(CrossRec) + sizeof(uint32_t));
-  if (lds < 2 * 64 * 64) lds = 2 * 64 * 64;   // the staged store of the results: 64 bytes per lane and spectrum
+  lds = p16_lds_bytes(n_pairs);
   return DEXCT_OK;
 }
 
@@ -633,10 +802,11 @@ int dexct_siddon_project_packed_skip(const dexct_fan_geom* geom, const dexct_ray
   proj::copy_noise(l.pa, view_begin, nl);     // (rows16_kernel draws the sample itself: PackedArgs, not its ProjArgs)
   l.t = Tables{mu, weights, weights2};
   l.st = as_stream(stream);
+  l.staged_store = proj::read_knob(proj::knob::kP16Staged) != 0;
   const bool noisy = weights2 != nullptr;
   // whole-line stores through LDS (STAGED) wherever the output allows them: row-fastest layout, whole groups of 4 rows,
   // one or two spectra (what the stage holds)
-  const bool staged = l.pa.staged_store && layout == 1 && geom->n_rows % 4 == 0 && n_spectra <= 2;
+  const bool staged = l.staged_store && layout == 1 && geom->n_rows % 4 == 0 && n_spectra <= 2;
   // rows16_kernel<NM, MINW, false, STAGED, NOISY>: MINW is 4 for two and three materials, 3 for four.  (The order of the arms
   // is the order in which the kernels are instantiated, hence their order in the code object.)
   // with the air-column map: the SKIP forms (instantiated after all the others, below); the DEXCT_P16_MINW forms have none
