@@ -24,6 +24,9 @@ SYMBOLS = ['dexct_strerror', 'dexct_abi_version', 'dexct_last_hip_error', 'dexct
 # the size queries return int64_t; dexct_strerror a string; every other entry point an int status
 SIZE_QUERIES = ['dexct_cone_layout_bytes', 'dexct_gn_workspace_bytes', 'dexct_gn_multi_workspace_bytes',
                 'dexct_gn_cov_workspace_bytes']
+# what include/dexct_gn_dedup.h declares (additive to ABI 6: the lists above are those of include/dexct.h): the entry point
+# (int status) and its size query (int64_t); load() requires and types them like the others
+GN_DEDUP_SYMBOLS = ['dexct_gn_decompose_dedup', 'dexct_gn_dedup_workspace_bytes']
 
 
 class FanGeom(C.Structure):
@@ -73,6 +76,7 @@ GN_FLAG_FULL_LOOP, GN_FLAG_NATURAL_ORDER, GN_FLAG_ONE_STEP, GN_FLAG_FULL_RESIDUA
 GN_REDUCED_HEADER = 16   # DEXCT_GN_REDUCED_HEADER
 GN_WS_EXECUTED, GN_WS_PROGRESS, GN_WS_QUEUE_HEAD, GN_WS_STALLS, GN_WS_RESIDUAL_ROWS = 72, 80, 88, 96, 104   # DEXCT_GN_WS_*: byte offsets
 GN_WS_WORDS = slice(GN_WS_EXECUTED, GN_WS_RESIDUAL_ROWS + 8)   # ... of the workspace's diagnostic uint64 words; the span of all five
+GN_DEDUP_USE, GN_DEDUP_FRESH, GN_DEDUP_CAP = 0, 8, 16   # DEXCT_GN_DEDUP_*: byte offsets of the dedup workspace's descriptor words
 GN_TABLE_ROW = 14        # doubles per energy row of the Newton tables (csrc/gn.hip, kTab)
 GN_MAX_MEAS, GN_MAX_MATS = 4, 3   # DEXCT_GN_MAX_MEAS, DEXCT_GN_MAX_MATS (dexct_gn_decompose_multi)
 GN_MULTI_FULL_LOOP = 1   # DEXCT_GN_MULTI_FULL_LOOP
@@ -128,7 +132,7 @@ def load():
                          f'(run `python -c "import __graft_entry__ as g; g.build()"` or `make -C dex-ct-sim_amd/csrc`). '
                          f'There is no CPU fallback.')
     lib = C.CDLL(LIB_PATH)
-    for name in SYMBOLS:
+    for name in SYMBOLS + GN_DEDUP_SYMBOLS:
         if not hasattr(lib, name):
             raise DexctError(f'{LIB_PATH} does not export {name}')
     lib.dexct_strerror.restype = C.c_char_p
@@ -195,6 +199,8 @@ def load():
     lib.dexct_siddon_trace.argtypes = [C.POINTER(FanGeom), vp, vp, i32, i32, vp, vp, vp, vp]
     lib.dexct_gn_decompose.argtypes = [vp, vp, i32, i64, vp, vp, i32, i32, i32, i32, i32, i32, vp, f64, vp, C.POINTER(GnOptions), vp, vp]
     lib.dexct_gn_workspace_bytes.argtypes = [i32, i32]
+    lib.dexct_gn_decompose_dedup.argtypes = lib.dexct_gn_decompose.argtypes[:-1] + [vp, vp]
+    lib.dexct_gn_dedup_workspace_bytes.argtypes = [i64, i32, i32]
     lib.dexct_gn_apply_mask.argtypes = [vp, i32, i64, f64, vp, vp]
     lib.dexct_gn_model_sums.argtypes = [vp, i64, vp, vp, i32, vp, vp, vp, vp]
     lib.dexct_reduce_max.argtypes = [vp, i32, i64, vp, vp]
@@ -206,6 +212,7 @@ def load():
     lib.dexct_gn_cov_workspace_bytes.argtypes = [i32, i32, i32]
     for name in SYMBOLS[1:]:
         getattr(lib, name).restype = i64 if name in SIZE_QUERIES else C.c_int
+    lib.dexct_gn_decompose_dedup.restype, lib.dexct_gn_dedup_workspace_bytes.restype = C.c_int, i64
     _lib = lib
     return lib
 

@@ -22,6 +22,7 @@
 
 #include "common.h"
 #include "exp_table.h"
+#include "gn_dedup.h"
 
 namespace dexct {
 
@@ -1685,11 +1686,12 @@ struct GnEnv {
   int sort;                 // DEXCT_GN_SORT=0: natural order of the hand-out on small sinograms
   int tiles_per_fetch;      // DEXCT_GN_TILES_PER_FETCH=<n>: queue positions per reservation (0: by size)
   int reduced;              // DEXCT_GN_REDUCED=0: the chord residual over the full tables (DEXCT_GN_FLAG_FULL_RESIDUAL on every call)
+  int dedup;                // DEXCT_GN_DEDUP=0: dexct_gn_decompose_dedup takes the direct route, without a probe
 };
 
 static const GnEnv& gn_env() {
   static const GnEnv env = [] {
-    GnEnv e{0, DEXCT_GN_DEFAULT_STOP_TOL, 0, kCoopBelowDefault, 1, 0, 1};
+    GnEnv e{0, DEXCT_GN_DEFAULT_STOP_TOL, 0, kCoopBelowDefault, 1, 0, 1, 1};
     auto flag = [](const char* name, char c) { const char* v = getenv(name); return v && v[0] == c; };
     auto number = [](const char* name, long long lo, long long hi, long long dflt) {
       const char* v = getenv(name);
@@ -1711,6 +1713,7 @@ static const GnEnv& gn_env() {
     e.sort = !flag("DEXCT_GN_SORT", '0');
     e.tiles_per_fetch = (int)number("DEXCT_GN_TILES_PER_FETCH", 1, 1024, 0);
     e.reduced = !flag("DEXCT_GN_REDUCED", '0');
+    e.dedup = !flag("DEXCT_GN_DEDUP", '0');
     return e;
   }();
   return env;
@@ -1869,22 +1872,16 @@ static GnGrid gn_grid(const GnTiling& tl, int pass, bool coop, const dexct_gn_op
   return GnGrid{nb, tiles_per_fetch};
 }
 
-extern "C" {
-
-int64_t dexct_gn_workspace_bytes(int32_t n_energies, int32_t n_bins) {
-  if (n_energies <= 0 || n_bins <= 0) return 0;
-  return (int64_t)gn_ws_tables_bytes(n_energies, n_bins) + (int64_t)kSortBuckets * sizeof(int) +
-         (int64_t)kMaxSortTiles * (sizeof(int) + sizeof(unsigned short));
-}
-
-int dexct_gn_decompose(const void* g1, const void* g2, int32_t g_is_f64, int64_t n_pix, const double* i0,
-                       const double* mus, int32_t n_energies, int32_t n_bins, int32_t bin_div, int32_t n_iters,
-                       int32_t precision, int32_t n_polish, const double* mask_max, double mask_frac, double* out_a,
-                       const dexct_gn_options* options, void* workspace, void* stream) {
+// dexct_gn_decompose, and with a dedup workspace dexct_gn_decompose_dedup: one body for both.
+static int gn_decompose_run(const void* g1, const void* g2, int32_t g_is_f64, int64_t n_pix, const double* i0,
+                            const double* mus, int32_t n_energies, int32_t n_bins, int32_t bin_div, int32_t n_iters,
+                            int32_t precision, int32_t n_polish, const double* mask_max, double mask_frac, double* out_a,
+                            const dexct_gn_options* options, void* workspace, void* dedup_workspace, void* stream) {
   const GnTiling tl = gn_tiling(n_pix, options);
   if (const int err = gn_check_call(g1, g2, n_pix, i0, mus, n_energies, n_bins, bin_div, n_iters, precision, n_polish, out_a, options,
                                     workspace, tl))
     return err;
+  if (reinterpret_cast<uintptr_t>(dedup_workspace) & 15u) return DEXCT_EINVAL;      // its results leave and arrive as 16-byte pieces
   const int pass = options ? options->pass : 0, oflags = options ? options->flags : 0;
   const double* start = (pass == DEXCT_GN_PASS_SHORTCUT) ? options->start : nullptr;
   hipStream_t st = as_stream(stream);
@@ -1918,26 +1915,83 @@ int dexct_gn_decompose(const void* g1, const void* g2, int32_t g_is_f64, int64_t
       sorted = true;
     }
     const int kflags = exact_exit | (sorted ? kFlagSorted : 0) | kFlagConfirm | (coop ? 0 : gg.tiles_per_fetch << kFlagFetchShift);
-    auto launch = [&](auto kernel, int threads, int flags, auto... last) {      // the queue kernels share their arguments up to `counters`
-      hipLaunchKernelGGL(kernel, dim3((unsigned)gg.blocks), dim3(threads), 0, st, g1, g2, g_is_f64, (long long)n_pix, (const double*)ws,
-                         n_energies, n_iters, tl, mask_max, mask_frac, flags, tol, out_a, counters, last...);
+    // the Newton launch of this call's pass on n pixels (a1, a2) in the tiling t: the sinograms', or the list's of the dedup route
+    auto newton = [&](const void* a1, const void* a2, int64_t n, const GnTiling& t, const GnGrid& g, int kf, double* out) {
+      auto launch = [&](auto kernel, int threads, int flags, auto... last) {      // the queue kernels share their arguments up to `counters`
+        hipLaunchKernelGGL(kernel, dim3((unsigned)g.blocks), dim3(threads), 0, st, a1, a2, g_is_f64, (long long)n, (const double*)ws,
+                           n_energies, n_iters, t, mask_max, mask_frac, flags, tol, out, counters, last...);
+      };
+      if (pass == DEXCT_GN_PASS_COUNT)
+        launch(gn_refill_kernel<true>, kGnBlock, kf, options->iterations);
+      else if (pass == DEXCT_GN_PASS_SHORTCUT && (oflags & DEXCT_GN_FLAG_ONE_STEP))
+        launch(gn_shortcut_kernel<1>, kGnBlock, kf | ((env.reduced && !(oflags & DEXCT_GN_FLAG_FULL_RESIDUAL)) ? kFlagReduced : 0), start);
+      else if (pass == DEXCT_GN_PASS_SHORTCUT)
+        launch(gn_shortcut_kernel<2>, kGnBlock, kf, start);
+      else if (coop)
+        launch(gn_coop_kernel, kCoopWaves * kWave, kf);
+      else
+        launch(gn_refill_kernel<false>, kGnBlock, kf, (unsigned char*)nullptr);
     };
-    if (pass == DEXCT_GN_PASS_COUNT)
-      launch(gn_refill_kernel<true>, kGnBlock, kflags, options->iterations);
-    else if (pass == DEXCT_GN_PASS_SHORTCUT && (oflags & DEXCT_GN_FLAG_ONE_STEP))
-      launch(gn_shortcut_kernel<1>, kGnBlock, kflags | ((env.reduced && !(oflags & DEXCT_GN_FLAG_FULL_RESIDUAL)) ? kFlagReduced : 0), start);
-    else if (pass == DEXCT_GN_PASS_SHORTCUT)
-      launch(gn_shortcut_kernel<2>, kGnBlock, kflags, start);
-    else if (coop)
-      launch(gn_coop_kernel, kCoopWaves * kWave, kflags);
-    else
-      launch(gn_refill_kernel<false>, kGnBlock, kflags, (unsigned char*)nullptr);
+    // The dedup route (gn_dedup.hip): the distinct pixels of every line go into a list, THIS pass's kernel - not a line of it
+    // changed - solves the list in plain tiling, natural order, and the results are expanded.  Which of the two Newton launches
+    // works is decided on the device: each starts with its queue head where the other's tiles are already handed out
+    // (list: the list is filled from the back, so the head is its first tile with entries; use = 0: its end), so one of them
+    // only fills lds_pow and leaves.
+    const bool dedup = dedup_workspace && env.dedup && pass != DEXCT_GN_PASS_COUNT && !coop && tl.transposed &&
+                       gn_dedup::sizes_allow(n_pix, tl.rows, tl.channels);
+    const GnDedupCall dc{dedup_workspace, n_pix, tl.rows, tl.channels, g_is_f64};
+    unsigned long long* words = reinterpret_cast<unsigned long long*>(ws);
+    if (dedup) {
+      if (const int err = gn_dedup_prepare(dc, g1, g2, st)) return err;
+      if (const int err = gn_dedup_list_head(dc, words + kWsQueueHead, st)) return err;
+      const gn_dedup::Layout y = dc.at();
+      const GnTiling list_tl = gn_tiling(y.cap, nullptr);
+      const GnGrid list_gg = gn_grid(list_tl, pass, false, options, env);
+      newton(dc.array<char>(y.list1), dc.array<char>(y.list2), y.cap, list_tl, list_gg,
+             exact_exit | kFlagConfirm | (list_gg.tiles_per_fetch << kFlagFetchShift), dc.array<double>(y.results));
+      DEXCT_LAUNCH_CHECK();
+      if (const int err = gn_dedup_direct_head(dc, words + kWsQueueHead, words + kWsProgress, tl.n_tiles, st)) return err;
+    }
+    newton(g1, g2, n_pix, tl, gg, kflags, out_a);
+    if (dedup) {
+      DEXCT_LAUNCH_CHECK();
+      if (const int err = gn_dedup_expand(dc, out_a, words + kWsProgress, st)) return err;
+    }
   } else {
     hipLaunchKernelGGL((gn_kernel<true, false>), grid, block, 0, st, g1, g2, g_is_f64, n_pix, (const double*)ws,
                        n_energies, n_iters, n_polish, 1, 1, mask_max, mask_frac, exact_exit, 0.0, tl, out_a);
   }
   DEXCT_LAUNCH_CHECK();
   return DEXCT_OK;
+}
+
+extern "C" {
+
+int64_t dexct_gn_workspace_bytes(int32_t n_energies, int32_t n_bins) {
+  if (n_energies <= 0 || n_bins <= 0) return 0;
+  return (int64_t)gn_ws_tables_bytes(n_energies, n_bins) + (int64_t)kSortBuckets * sizeof(int) +
+         (int64_t)kMaxSortTiles * (sizeof(int) + sizeof(unsigned short));
+}
+
+int dexct_gn_decompose(const void* g1, const void* g2, int32_t g_is_f64, int64_t n_pix, const double* i0,
+                       const double* mus, int32_t n_energies, int32_t n_bins, int32_t bin_div, int32_t n_iters,
+                       int32_t precision, int32_t n_polish, const double* mask_max, double mask_frac, double* out_a,
+                       const dexct_gn_options* options, void* workspace, void* stream) {
+  return gn_decompose_run(g1, g2, g_is_f64, n_pix, i0, mus, n_energies, n_bins, bin_div, n_iters, precision, n_polish, mask_max, mask_frac,
+                          out_a, options, workspace, nullptr, stream);
+}
+
+int64_t dexct_gn_dedup_workspace_bytes(int64_t n_pix, int32_t rows, int32_t g_is_f64) {
+  if (n_pix <= 0 || rows < 1 || n_pix % rows != 0) return 0;
+  return gn_dedup::layout(n_pix, rows, g_is_f64 ? 8 : 4).bytes;
+}
+
+int dexct_gn_decompose_dedup(const void* g1, const void* g2, int32_t g_is_f64, int64_t n_pix, const double* i0,
+                             const double* mus, int32_t n_energies, int32_t n_bins, int32_t bin_div, int32_t n_iters,
+                             int32_t precision, int32_t n_polish, const double* mask_max, double mask_frac, double* out_a,
+                             const dexct_gn_options* options, void* workspace, void* dedup_workspace, void* stream) {
+  return gn_decompose_run(g1, g2, g_is_f64, n_pix, i0, mus, n_energies, n_bins, bin_div, n_iters, precision, n_polish, mask_max, mask_frac,
+                          out_a, options, workspace, dedup_workspace, stream);
 }
 
 int dexct_gn_model_sums(const double* a, int64_t n_states, const double* i0, const double* mus, int32_t n_energies,

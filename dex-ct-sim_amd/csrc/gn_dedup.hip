@@ -1,0 +1,335 @@
+// dexct_gn_decompose_dedup: solve repeated rows once, expand the results.
+//
+// The result of a float64 shared-spectrum Newton kernel is a pure function of a pixel's two counts (and the mask threshold).  In
+// an extruded phantom most rows of a (view, channel) line carry bitwise the counts of the row below.  The passes here find the
+// pixels that differ from the row before (FRESH), copy their counts into a list, and - after the unchanged Newton kernel has
+// solved the list - write every pixel's result from the list's.  The index arithmetic is gn_dedup_index.h; the Newton launches
+// and the order of it all are dexct_gn_decompose's host code (gn.hip).
+//
+//   probe    every 64th line: fresh pixels of the sample -> use = (share <= 1 / 8).  The only pass an input without repeats
+//            pays: every kernel below returns at once when use = 0.
+//   census   one bit per pixel (a 64-bit word per 64 rows of a line), one count per line
+//   scan     exclusive scan of the counts (block sums, scan of the sums, bases): F; F > cap -> use = 0
+//   gather   fresh pixel j -> list place cap - F + j; the places before it in its tile get the count 1.0
+//   expand   pixel -> result place cap - F + base[line] + rank in the line - 1, tiles of 16 channels x 64 rows through LDS,
+//            256-byte runs along the channels, non-temporal; a block walks up a column of tiles
+#include "gn_dedup.h"
+
+namespace dexct {
+namespace {
+
+using namespace gn_dedup;
+
+constexpr int kBlock = 256, kWavesPerBlock = kBlock / kWave;
+constexpr int kMaxGrid = 2048;                   // the line and tile loops stride: a grid that returns at once stays cheap
+constexpr int kExpandC = 16, kExpandR = kWordBits;       // the expansion's tile: channels x rows
+typedef double d2 __attribute__((ext_vector_type(2)));
+
+template <typename B> __device__ __forceinline__ B one_bits();
+template <> __device__ __forceinline__ uint32_t one_bits<uint32_t>() { return 0x3F800000u; }
+template <> __device__ __forceinline__ uint64_t one_bits<uint64_t>() { return 0x3FF0000000000000ull; }
+
+// the ballot of "row r0 + lane of the line at `at` is fresh" (rows beyond the line: 0).  The four loads are unconditional - a row
+// beyond the line reads the last one - so that the loads of several calls can be in flight together.
+template <typename B>
+__device__ __forceinline__ unsigned long long fresh_ballot(const B* __restrict__ g1, const B* __restrict__ g2, long long at, int r0,
+                                                           int rows, int lane, bool valid = true) {
+  const int r = r0 + lane, rc = r < rows ? r : rows - 1, rp = rc > 0 ? rc - 1 : 0;
+  const B x1 = g1[at + rc], p1 = g1[at + rp], x2 = g2[at + rc], p2 = g2[at + rp];
+  return __ballot(valid && r < rows && (r == 0 || x1 != p1 || x2 != p2));
+}
+
+// The probe.  Its work items are the 64-row words of the sampled lines, four of them in flight per wave; the blocks meet in ONE
+// word, (blocks done << 40) + fresh pixels, so that a block pays one atomic and the last one holds the total.
+constexpr int kProbeUnroll = 4, kProbeMaxGrid = 1024, kProbeDoneShift = 40;
+
+template <typename B>
+__global__ __launch_bounds__(kBlock) void gn_dedup_probe_kernel(const B* __restrict__ g1, const B* __restrict__ g2, long long n_sampled,
+                                                                 int rows, long long cap, unsigned long long* __restrict__ desc) {
+  __shared__ unsigned s_cnt[kWavesPerBlock];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, n_words = words_per_line(rows);
+  const long long n_items = n_sampled * n_words, n_waves = (long long)gridDim.x * kWavesPerBlock;
+  unsigned cnt = 0u;
+  for (long long i0 = (long long)blockIdx.x * kWavesPerBlock + wv; i0 < n_items; i0 += kProbeUnroll * n_waves) {
+    unsigned long long m[kProbeUnroll];
+#pragma unroll
+    for (int j = 0; j < kProbeUnroll; ++j) {
+      const long long i = i0 + j * n_waves, ic = i < n_items ? i : n_items - 1;
+      const long long s = ic / n_words;
+      m[j] = fresh_ballot(g1, g2, s * kProbeStride * rows, row_of((int)(ic - s * n_words), 0), rows, lane, i < n_items);
+    }
+#pragma unroll
+    for (int j = 0; j < kProbeUnroll; ++j) cnt += (unsigned)__popcll(m[j]);
+  }
+  if (lane == 0) s_cnt[wv] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long mine = 1ull << kProbeDoneShift;
+    for (int k = 0; k < kWavesPerBlock; ++k) mine += s_cnt[k];
+    const unsigned long long all = atomicAdd(&desc[kDescProbeFresh], mine) + mine;
+    if ((all >> kProbeDoneShift) == (unsigned long long)gridDim.x) {        // the last block: the verdict
+      const unsigned long long fresh = all & ((1ull << kProbeDoneShift) - 1ull), pixels = (unsigned long long)n_sampled * rows;
+      desc[kDescProbeFresh] = fresh;
+      desc[kDescProbeDone] = (unsigned long long)gridDim.x;
+      desc[kDescProbePixels] = pixels;
+      desc[kDescCap] = (unsigned long long)cap;
+      desc[kDescFresh] = 0ull;
+      desc[kDescUse] = probe_votes_use(fresh, pixels) ? 1ull : 0ull;
+    }
+  }
+}
+
+template <typename B>
+__global__ __launch_bounds__(kBlock) void gn_dedup_census_kernel(const B* __restrict__ g1, const B* __restrict__ g2, long long n_lines,
+                                                                  int rows, const unsigned long long* __restrict__ desc,
+                                                                  unsigned long long* __restrict__ bits, unsigned* __restrict__ counts) {
+  if (desc[kDescUse] == 0ull) return;
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, n_words = words_per_line(rows);
+  for (long long line = (long long)blockIdx.x * kWavesPerBlock + wv; line < n_lines; line += (long long)gridDim.x * kWavesPerBlock) {
+    unsigned cnt = 0u;
+    for (int k = 0; k < n_words; ++k) {
+      const unsigned long long m = fresh_ballot(g1, g2, line * rows, row_of(k, 0), rows, lane);
+      if (lane == 0) bits[word_index(line, rows, k)] = m;
+      cnt += (unsigned)__popcll(m);
+    }
+    if (lane == 0) counts[line] = cnt;
+  }
+}
+
+// exclusive scan of one value per thread over a block of N threads (s: N words of LDS); *total: the block's sum
+template <int N>
+__device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned* s, unsigned* total) {
+  const int t = threadIdx.x;
+  s[t] = v;
+  __syncthreads();
+  unsigned x = v;
+  for (int d = 1; d < N; d <<= 1) {
+    const unsigned y = t >= d ? s[t - d] : 0u;
+    __syncthreads();
+    x += y;
+    s[t] = x;
+    __syncthreads();
+  }
+  *total = s[N - 1];
+  __syncthreads();
+  return x - v;
+}
+
+constexpr int kScanPerThread = kScanBlock / kBlock;
+
+// the fresh pixels of each block of kScanBlock lines
+__global__ __launch_bounds__(kBlock) void gn_dedup_sums_kernel(const unsigned* __restrict__ counts, long long n_lines,
+                                                                const unsigned long long* __restrict__ desc, unsigned* __restrict__ sums) {
+  if (desc[kDescUse] == 0ull) return;
+  __shared__ unsigned s[kBlock];
+  const long long first = (long long)blockIdx.x * kScanBlock + threadIdx.x * kScanPerThread;
+  unsigned v = 0u;
+  for (int q = 0; q < kScanPerThread; ++q) v += first + q < n_lines ? counts[first + q] : 0u;
+  unsigned total;
+  block_exclusive_scan<kBlock>(v, s, &total);
+  if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// one block: the sums become the blocks' bases; F; the list's capacity decides
+__global__ __launch_bounds__(1024) void gn_dedup_scan_kernel(unsigned* __restrict__ sums, long long n_blocks,
+                                                              unsigned long long* __restrict__ desc) {
+  if (desc[kDescUse] == 0ull) return;
+  __shared__ unsigned s[1024];
+  unsigned long long carry = 0ull;
+  for (long long b0 = 0; b0 < n_blocks; b0 += 1024) {
+    const long long b = b0 + threadIdx.x;
+    const unsigned v = b < n_blocks ? sums[b] : 0u;
+    unsigned total;
+    const unsigned ex = block_exclusive_scan<1024>(v, s, &total);
+    if (b < n_blocks) sums[b] = (unsigned)carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) {
+    desc[kDescFresh] = carry;
+    if (!list_fits((int64_t)carry, (int64_t)desc[kDescCap])) desc[kDescUse] = 0ull;
+  }
+}
+
+// base[line] = fresh pixels of all earlier lines
+__global__ __launch_bounds__(kBlock) void gn_dedup_bases_kernel(const unsigned* __restrict__ counts, long long n_lines,
+                                                                 const unsigned long long* __restrict__ desc,
+                                                                 const unsigned* __restrict__ sums, unsigned* __restrict__ bases) {
+  if (desc[kDescUse] == 0ull) return;
+  __shared__ unsigned s[kBlock];
+  const long long first = (long long)blockIdx.x * kScanBlock + threadIdx.x * kScanPerThread;
+  unsigned c[kScanPerThread], v = 0u;
+  for (int q = 0; q < kScanPerThread; ++q) {
+    c[q] = first + q < n_lines ? counts[first + q] : 0u;
+    v += c[q];
+  }
+  unsigned total;
+  unsigned run = sums[blockIdx.x] + block_exclusive_scan<kBlock>(v, s, &total);
+  for (int q = 0; q < kScanPerThread; ++q) {
+    if (first + q < n_lines) bases[first + q] = run;
+    run += c[q];
+  }
+}
+
+template <typename B>
+__global__ __launch_bounds__(kBlock) void gn_dedup_gather_kernel(const B* __restrict__ g1, const B* __restrict__ g2, long long n_lines,
+                                                                  int rows, const unsigned long long* __restrict__ desc,
+                                                                  const unsigned long long* __restrict__ bits,
+                                                                  const unsigned* __restrict__ bases, B* __restrict__ list1,
+                                                                  B* __restrict__ list2) {
+  if (desc[kDescUse] == 0ull) return;
+  const long long n_fresh = (long long)desc[kDescFresh], cap = (long long)desc[kDescCap];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, n_words = words_per_line(rows);
+  if (blockIdx.x == 0 && wv == 0) {                      // the places that share the first entry's tile
+    const long long p = pad_begin(cap, n_fresh) + lane;
+    if (p < pad_end(cap, n_fresh)) { list1[p] = one_bits<B>(); list2[p] = one_bits<B>(); }
+  }
+  for (long long line = (long long)blockIdx.x * kWavesPerBlock + wv; line < n_lines; line += (long long)gridDim.x * kWavesPerBlock) {
+    const long long base = bases[line];
+    int before = 0;
+    for (int k = 0; k < n_words; ++k) {
+      const unsigned long long word = bits[word_index(line, rows, k)];
+      if ((word >> lane) & 1ull) {                       // (a set bit is a row of the line: the census sets no other)
+        const long long to = result_place(cap, n_fresh, base, rank_inclusive(before, word, lane)), from = line * rows + row_of(k, lane);
+        list1[to] = g1[from];
+        list2[to] = g2[from];
+      }
+      before += (int)__popcll(word);
+    }
+  }
+}
+
+// *head: where the tile queue of the next Newton launch starts
+__global__ void gn_dedup_list_head_kernel(const unsigned long long* __restrict__ desc, unsigned long long* __restrict__ head) {
+  *head = (unsigned long long)list_queue_head((int64_t)desc[kDescCap], (int64_t)desc[kDescFresh], desc[kDescUse] != 0ull);
+}
+
+__global__ void gn_dedup_direct_head_kernel(const unsigned long long* __restrict__ desc, unsigned long long* __restrict__ head,
+                                            unsigned long long* __restrict__ progress, long long direct_tiles) {
+  const bool use = desc[kDescUse] != 0ull;
+  *head = (unsigned long long)direct_queue_head(direct_tiles, use);
+  if (use) *progress = 0ull;                             // (the list's pixels; the expansion counts the sinograms')
+}
+
+__global__ __launch_bounds__(kBlock) void gn_dedup_expand_kernel(const unsigned long long* __restrict__ desc,
+                                                                  const unsigned long long* __restrict__ bits,
+                                                                  const unsigned* __restrict__ bases, const d2* __restrict__ results,
+                                                                  long long n_views, int rows, int channels, d2* __restrict__ out_a,
+                                                                  unsigned long long* __restrict__ progress) {
+  if (desc[kDescUse] == 0ull) return;
+  __shared__ d2 tile[kExpandC][kExpandR + 1];            // (+ 1: the channel-wise reads spread over the banks)
+  const long long n_fresh = (long long)desc[kDescFresh], cap = (long long)desc[kDescCap];
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int tiles_r = words_per_line(rows), tiles_c = (channels + kExpandC - 1) / kExpandC;
+  constexpr int kPerWave = kExpandC / kWavesPerBlock;
+  unsigned long long written = 0ull;
+  // a block takes a COLUMN of tiles - 16 channels of a view, all rows - from the first row up: the fresh pixels of a line before
+  // the tile's word are then a running sum, not a loop over the earlier words
+  for (long long col = blockIdx.x; col < n_views * tiles_c; col += gridDim.x) {
+    const int cb = (int)(col % tiles_c);
+    const long long v = col / tiles_c;
+    // (the loads below are unconditional - a channel beyond the last reads the last, a row beyond the line the line's last
+    // entry - so that the wave's four lines are in flight together)
+    long long line[kPerWave], base[kPerWave];
+    int before[kPerWave];
+#pragma unroll
+    for (int q = 0; q < kPerWave; ++q) {
+      const int c = cb * kExpandC + wv * kPerWave + q;
+      line[q] = v * channels + (c < channels ? c : channels - 1);
+      base[q] = bases[line[q]];
+      before[q] = 0;
+    }
+    for (int rb = 0; rb < tiles_r; ++rb) {
+      // in: a wave reads 64 rows of a line at a time (neighbouring lanes: the same or neighbouring entries of the results)
+      d2 val[kPerWave];
+#pragma unroll
+      for (int q = 0; q < kPerWave; ++q) {
+        const unsigned long long word = bits[word_index(line[q], rows, rb)];
+        val[q] = results[result_place(cap, n_fresh, base[q], rank_inclusive(before[q], word, lane))];
+        before[q] += (int)__popcll(word);
+      }
+#pragma unroll
+      for (int q = 0; q < kPerWave; ++q) tile[wv * kPerWave + q][lane] = val[q];
+      __syncthreads();
+      // out: 16 lanes write the 16 channels of a row, 256 bytes
+      const int co = threadIdx.x % kExpandC, c = cb * kExpandC + co;
+      for (int k = 0; k < kExpandR / (kBlock / kExpandC); ++k) {
+        const int ro = threadIdx.x / kExpandC + k * (kBlock / kExpandC), r = row_of(rb, ro);
+        if (c < channels && r < rows) __builtin_nontemporal_store(tile[co][ro], out_a + ((v * rows + r) * channels + c));
+      }
+      __syncthreads();
+    }
+    const int nc = channels - cb * kExpandC < kExpandC ? channels - cb * kExpandC : kExpandC;
+    written += (unsigned long long)nc * rows;
+  }
+  if (threadIdx.x == 0 && written) atomicAdd(progress, written);
+}
+
+unsigned capped_grid(long long n) { return (unsigned)(n < 1 ? 1 : (n > kMaxGrid ? kMaxGrid : n)); }
+
+template <typename B>
+int prepare(const GnDedupCall& dc, const void* g1v, const void* g2v, hipStream_t st) {
+  const Layout y = dc.at();
+  const B* g1 = reinterpret_cast<const B*>(g1v);
+  const B* g2 = reinterpret_cast<const B*>(g2v);
+  unsigned long long* desc = dc.array<unsigned long long>(y.desc);
+  unsigned long long* bits = dc.array<unsigned long long>(y.bits);
+  unsigned* counts = dc.array<unsigned>(y.counts);
+  unsigned* bases = dc.array<unsigned>(y.bases);
+  unsigned* sums = dc.array<unsigned>(y.sums);
+  DEXCT_HIP_TRY(hipMemsetAsync(desc, 0, kDescWords * sizeof(unsigned long long), st));
+  const long long n_sampled = probe_lines(y.n_lines), line_blocks = (y.n_lines + kWavesPerBlock - 1) / kWavesPerBlock;
+  const long long probe_blocks = (n_sampled * words_per_line(dc.rows) + kWavesPerBlock * kProbeUnroll - 1) / (kWavesPerBlock * kProbeUnroll);
+  hipLaunchKernelGGL(gn_dedup_probe_kernel<B>, dim3((unsigned)(probe_blocks > kProbeMaxGrid ? kProbeMaxGrid : probe_blocks)), dim3(kBlock), 0, st,
+                     g1, g2, n_sampled, dc.rows, (long long)y.cap, desc);
+  DEXCT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gn_dedup_census_kernel<B>, dim3(capped_grid(line_blocks)), dim3(kBlock), 0, st, g1, g2, (long long)y.n_lines, dc.rows,
+                     (const unsigned long long*)desc, bits, counts);
+  DEXCT_LAUNCH_CHECK();
+  const long long n_blocks = scan_blocks(y.n_lines);
+  hipLaunchKernelGGL(gn_dedup_sums_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, st, (const unsigned*)counts, (long long)y.n_lines,
+                     (const unsigned long long*)desc, sums);
+  DEXCT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gn_dedup_scan_kernel, dim3(1), dim3(1024), 0, st, sums, n_blocks, desc);
+  DEXCT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gn_dedup_bases_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, st, (const unsigned*)counts, (long long)y.n_lines,
+                     (const unsigned long long*)desc, (const unsigned*)sums, bases);
+  DEXCT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(gn_dedup_gather_kernel<B>, dim3(capped_grid(line_blocks)), dim3(kBlock), 0, st, g1, g2, (long long)y.n_lines, dc.rows,
+                     (const unsigned long long*)desc, (const unsigned long long*)bits, (const unsigned*)bases, dc.array<B>(y.list1),
+                     dc.array<B>(y.list2));
+  DEXCT_LAUNCH_CHECK();
+  return DEXCT_OK;
+}
+
+}  // namespace
+
+int gn_dedup_prepare(const GnDedupCall& dc, const void* g1, const void* g2, hipStream_t st) {
+  return dc.g_is_f64 ? prepare<uint64_t>(dc, g1, g2, st) : prepare<uint32_t>(dc, g1, g2, st);
+}
+
+int gn_dedup_list_head(const GnDedupCall& dc, unsigned long long* head, hipStream_t st) {
+  hipLaunchKernelGGL(gn_dedup_list_head_kernel, dim3(1), dim3(1), 0, st, (const unsigned long long*)dc.array<unsigned long long>(dc.at().desc), head);
+  DEXCT_LAUNCH_CHECK();
+  return DEXCT_OK;
+}
+
+int gn_dedup_direct_head(const GnDedupCall& dc, unsigned long long* head, unsigned long long* progress, int64_t direct_tiles, hipStream_t st) {
+  hipLaunchKernelGGL(gn_dedup_direct_head_kernel, dim3(1), dim3(1), 0, st, (const unsigned long long*)dc.array<unsigned long long>(dc.at().desc),
+                     head, progress, (long long)direct_tiles);
+  DEXCT_LAUNCH_CHECK();
+  return DEXCT_OK;
+}
+
+int gn_dedup_expand(const GnDedupCall& dc, double* out_a, unsigned long long* progress, hipStream_t st) {
+  const Layout y = dc.at();
+  const long long n_views = dc.n_pix / ((long long)dc.rows * dc.channels);
+  const long long n_columns = n_views * ((dc.channels + kExpandC - 1) / kExpandC);
+  hipLaunchKernelGGL(gn_dedup_expand_kernel, dim3(capped_grid(n_columns)), dim3(kBlock), 0, st,
+                     (const unsigned long long*)dc.array<unsigned long long>(y.desc), (const unsigned long long*)dc.array<unsigned long long>(y.bits),
+                     (const unsigned*)dc.array<unsigned>(y.bases), (const d2*)dc.array<d2>(y.results), n_views, dc.rows, dc.channels,
+                     reinterpret_cast<d2*>(out_a), progress);
+  DEXCT_LAUNCH_CHECK();
+  return DEXCT_OK;
+}
+
+}  // namespace dexct

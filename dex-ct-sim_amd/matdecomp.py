@@ -150,12 +150,15 @@ class GnAuditError(RuntimeError):
 class _GnRun:
     """What the most recent gn_device call left for diagnostics - or, with ``accumulate_stats``, ALL the chunk launches of a
     pipelined get_basismat_sinos call: per launch its workspace and its (before, after) events; of the latest launch the event
-    recorded after its counters were zeroed, the mode and the tables' n_e; the sampled audit, if one ran."""
-    __slots__ = ('workspaces', 'events', 'zeroed', 'mode', 'n_energies', 'audit')
+    recorded after its counters were zeroed, the mode and the tables' n_e; the sampled audit, if one ran; per launch of gn_device
+    the descriptor of its dedup workspace (None: dexct_gn_decompose, not dexct_gn_decompose_dedup)."""
+    __slots__ = ('workspaces', 'events', 'zeroed', 'mode', 'n_energies', 'audit', 'dedup')
 
     def __init__(self):
-        self.workspaces, self.events, self.zeroed, self.mode, self.n_energies, self.audit = [], [], None, 'single', 0, None
+        self.workspaces, self.events, self.zeroed, self.mode, self.n_energies, self.audit, self.dedup = [], [], None, 'single', 0, None, []
 
+
+DEDUP_MIN_ROWS, DEDUP_MIN_PIXELS = 64, 2 ** 22      # gn_device(dedup=None): below these the fixed launches of the dedup route outweigh any gain
 
 _last_run = None       # the process's only diagnostic state: None before the first call
 _table_cache = {}
@@ -169,7 +172,11 @@ def last_gn_stats():
     per-channel-spectrum kernels, which do not count.  ``mode``: 'one' / 'start' (the short cut), 'single', or 'exact (ill-posed
     pair)'; ``audit``: the last sampled audit, if any.  ``residual_energies``: the table rows the chord residual of the one-step
     launch summed per pixel, as the kernel reports it - the rows of the reduced residual rule where one is installed and not
-    switched off, else (and in every other mode) the tables' n_e."""
+    switched off, else (and in every other mode) the tables' n_e.  ``dedup``: None when no launch went through
+    dexct_gn_decompose_dedup (see gn_device), else what its descriptor says, summed over the launches that did: ``use`` (launches
+    that solved the list of distinct pixels and expanded it; 0: the direct launch ran), ``F`` (the distinct pixels counted; 0
+    where the probe said no), ``cap`` (the list's capacity), ``launches``.  With ``use`` the executed steps are those of the F
+    solved pixels, not of every unmasked pixel."""
     return _gn_stats(_last_run)
 
 
@@ -188,6 +195,12 @@ def _gn_stats(run):
         st['main_ms'] = sum(e[0].elapsed_time(e[1]) for e in run.events)
     if run.audit is not None:
         st['audit'] = run.audit
+    if run.dedup:               # (a record made by gn_device: one entry per launch)
+        used = [d for d in run.dedup if d is not None]
+        st['dedup'] = None
+        if used:
+            words = torch.stack([d.view(torch.int64) for d in used]).sum(dim=0).tolist()      # DEXCT_GN_DEDUP_USE, _FRESH, _CAP
+            st['dedup'] = {'use': int(words[0]), 'F': int(words[1]), 'cap': int(words[2]), 'launches': len(used)}
     return st
 
 
@@ -483,7 +496,7 @@ def _audit(run, g1, g2, a, i0, mus, n_iters, ppm, strict, out_rc, mask_max, mask
 
 def gn_device(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=None, bin_div=1, mask_max=None,
               mask_frac=0.95, stop_tol=None, out_rc=None, kernel=0, accumulate_stats=False, two_level=None, full_loop=False,
-              natural_order=False, blocks_per_cu=0, audit=None, audit_strict=None, reduced=None):
+              natural_order=False, blocks_per_cu=0, audit=None, audit_strict=None, reduced=None, dedup=None, dedup_workspace=None):
     """g1, g2: device tensors of equal shape; mus: [2, nE] float64; i0: [2, nE] (one spectrum for all
     pixels) or [2, nBins, nE] (pixel p uses row (p // bin_div) % nBins: the reference's general layout).
     ``mask_max``: device float64 scalar (the global maximum of sinogram 1) - pixels with g1 >= mask_frac * max are
@@ -499,12 +512,19 @@ def gn_device(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=N
     ``reduced``: None / True = the chord step of mode 'one' sums its residual over the reduced residual rule where one is installed
     for the pair (quadrature.residual_rule), False = over all energies (so does DEXCT_GN_REDUCED=0 in the environment, read once by
     the library); last_gn_stats()['residual_energies'] says which it was.
+    ``dedup``: the call goes through dexct_gn_decompose_dedup (rows that repeat the row before them bitwise are solved once,
+    include/dexct_gn_dedup.h; the same bytes either way) - None: where that route exists (float64, one spectrum, a lane kernel, ``out_rc``)
+    and can pay: rows >= DEDUP_MIN_ROWS and DEDUP_MIN_PIXELS pixels; True: wherever the library accepts a dedup workspace;
+    False: never.  last_gn_stats()['dedup'] says what the device then decided.  ``dedup_workspace``: a uint8 device tensor of at
+    least dexct_gn_dedup_workspace_bytes bytes to use for it (default: a new one; tests pass guarded, pre-filled ones).
     Returns a device tensor of shape g1.shape + (2,) float64 (with ``out_rc``: the last two sinogram dimensions swapped)."""
     global _last_run
-    a, ws, ev, zeroed, mode, n_e = _gn_launch(g1, g2, i0, mus, n_iters, precision, n_polish, out, bin_div, mask_max, mask_frac, stop_tol,
-                                              out_rc, kernel, two_level, full_loop, natural_order, blocks_per_cu, reduced)
+    a, ws, ev, zeroed, mode, n_e, dws = _gn_launch(g1, g2, i0, mus, n_iters, precision, n_polish, out, bin_div, mask_max, mask_frac,
+                                                   stop_tol, out_rc, kernel, two_level, full_loop, natural_order, blocks_per_cu, reduced,
+                                                   dedup, dedup_workspace)
     run = _last_run if accumulate_stats and _last_run is not None else _GnRun()
     run.workspaces.append(ws)
+    run.dedup.append(None if dws is None else dws[:24].clone())      # (the descriptor, copied on the stream: the 1.3 GB workspace is not kept alive)
     run.events.append(ev)
     run.zeroed, run.mode, run.n_energies = zeroed, mode, n_e
     _last_run = run
@@ -517,10 +537,10 @@ def gn_device(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=N
 
 def _gn_launch(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=None, bin_div=1, mask_max=None, mask_frac=0.95,
                stop_tol=None, out_rc=None, kernel=0, two_level=None, full_loop=False, natural_order=False, blocks_per_cu=0,
-               reduced=None):
-    """One dexct_gn_decompose launch with gn_device's arguments (see there): everything up to and including the call.  Touches no
-    module state.  Returns (result, workspace, (before, after) events, the event recorded after the counters were zeroed, mode,
-    n_e)."""
+               reduced=None, dedup=None, dedup_workspace=None):
+    """One dexct_gn_decompose (or dexct_gn_decompose_dedup) launch with gn_device's arguments (see there): everything up to and
+    including the call.  Touches no module state.  Returns (result, workspace, (before, after) events, the event recorded after
+    the counters were zeroed, mode, n_e, the dedup workspace or None)."""
     lib = _native.load()
     dev = g1.device
     precision = precision or DEFAULT_PRECISION
@@ -582,14 +602,31 @@ def _gn_launch(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=
         opts = _native.gn_options(stop_tol, rows, chans, 1, _native.GN_PASS_SHORTCUT, None, start.data_ptr(), flags, blocks_per_cu)
     else:
         opts = _native.gn_options(stop_tol, rows, chans, kernel, 0, None, None, flags, blocks_per_cu)
+    # the dedup route (include/dexct_gn_dedup.h): where the library has it - the lane kernels of the float64 shared-spectrum path, results
+    # in the reference's order - and, unless forced, where the lines are long and the sinograms large enough to pay for its
+    # fixed launches (the library takes the same decision again for what Python cannot see: DEXCT_GN_DEDUP=0, the cooperative
+    # kernel of small sinograms)
+    n_pix = g1.numel()
+    route = (precision == 'f64' and n_bins == 1 and rows > 0 and chans > 0 and n_pix < 2 ** 31 and n_pix // 8 >= 64
+             and (start is not None or kernel != 2))
+    if dedup is None:
+        dedup = route and rows >= DEDUP_MIN_ROWS and n_pix >= DEDUP_MIN_PIXELS
+    dws = None
+    if dedup and route:
+        need = lib.dexct_gn_dedup_workspace_bytes(n_pix, rows, is64)
+        dws = dedup_workspace if dedup_workspace is not None else torch.empty(need, dtype=torch.uint8, device=dev)
+        if dws.dtype != torch.uint8 or dws.numel() < need or not dws.is_contiguous() or dws.device != g1.device:
+            raise ValueError(f'dedup_workspace must be a contiguous uint8 tensor of at least {need} bytes on the sinograms\' device')
+        dws[:24].zero_()                  # (the descriptor reads 0 / 0 / 0 where the library takes the direct route without a probe)
+    args = (ptr(g1), ptr(g2), is64, n_pix, ptr(i0_d), ptr(mus_d), n_e, n_bins, int(bin_div), int(n_iters), int(precision == 'mixed'),
+            int(n_polish), ptr(mask_max), float(mask_frac), ptr(a), opts, ptr(ws))
     ev[0].record()
-    _native.check(lib.dexct_gn_decompose(ptr(g1), ptr(g2), is64, g1.numel(), ptr(i0_d),
-                                         ptr(mus_d), n_e, n_bins, int(bin_div), int(n_iters),
-                                         int(precision == 'mixed'), int(n_polish), ptr(mask_max), float(mask_frac), ptr(a),
-                                         opts, ptr(ws), stream_ptr()),
-                  'dexct_gn_decompose')
+    if dws is not None:
+        _native.check(lib.dexct_gn_decompose_dedup(*args, ptr(dws), stream_ptr()), 'dexct_gn_decompose_dedup')
+    else:
+        _native.check(lib.dexct_gn_decompose(*args, stream_ptr()), 'dexct_gn_decompose')
     ev[1].record()
-    return a, ws, ev, zeroed, mode, n_e
+    return a, ws, ev, zeroed, mode, n_e, dws
 
 
 def _progress_lines(run, n_views, n_bins, t0, every=20, poll_s=0.05):

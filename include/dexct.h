@@ -513,6 +513,11 @@ int dexct_gn_decompose(const void* g1, const void* g2, int32_t g_is_f64, int64_t
                        int32_t precision, int32_t n_polish, const double* mask_max, double mask_frac, double* out_a,
                        const dexct_gn_options* options, void* workspace, void* stream);
 
+/* dexct_gn_decompose that solves repeated rows once - dexct_gn_decompose_dedup, with a second workspace of about n_pix / 8 +
+ * n_pix x 3 (float32 counts) or 4 bytes + 8 per line (1.3 GB for 4.1e8 float32 pixels in lines of 512; its size query gives the
+ * exact figure) and the knob DEXCT_GN_DEDUP=0 - is additive to ABI 6 and declared, with its contract, in dexct_gn_dedup.h, which
+ * this header includes below: the declarations of ABI 6 stay the list they were. */
+
 /* The same decomposition for n_meas = 2 .. 4 measurements and n_mats = 2 .. 3 basis materials: the general form of
  * optimize_sino_cpu (matdecomp.py:87-127 sums over nMeas and inverts an nMats x nMats Hessian) - three tube voltages, three or
  * four photon-counting bins, a third basis with a K-edge.  Additive to ABI 6; dexct_gn_decompose is unchanged.
@@ -826,4 +831,7 @@ int dexct_pwls_update(const float* x_old, const float* g, const float* d, int32_
 #ifdef __cplusplus
 }
 #endif
+
+#include "dexct_gn_dedup.h"      /* additive to ABI 6: the Newton decomposition that solves repeated rows once */
+
 #endif /* DEXCT_H */

@@ -123,10 +123,11 @@ def valu(name, ph):
             print(f'{name}: launch with det_dedup={knob}, {n_e} energies', flush=True)
 
 
-for name, ph in volumes():
-    if mode == 'census':
-        census(name, ph)
-    elif mode == 'ab':
-        ab(name, ph, int(sys.argv[2]) if len(sys.argv) > 2 else 3)
-    else:
-        valu(name, ph)
+if __name__ == '__main__':              # (tools/probes/gn_dedup.py imports the volumes)
+    for name, ph in volumes():
+        if mode == 'census':
+            census(name, ph)
+        elif mode == 'ab':
+            ab(name, ph, int(sys.argv[2]) if len(sys.argv) > 2 else 3)
+        else:
+            valu(name, ph)
