@@ -10,9 +10,11 @@
 //            pays: every kernel below returns at once when use = 0.
 //   census   one bit per pixel (a 64-bit word per 64 rows of a line), one count per line
 //   scan     exclusive scan of the counts (block sums, scan of the sums, bases): F; F > cap -> use = 0
-//   gather   fresh pixel j -> list place cap - F + j; the places before it in its tile get the count 1.0
-//   expand   pixel -> result place cap - F + base[line] + rank in the line - 1, tiles of 16 channels x 64 rows through LDS,
-//            256-byte runs along the channels, non-temporal; a block walks up a column of tiles
+//   gather   fresh pixel j -> list place cap - F + j; the places before it in its tile get the count 1.0.  A block takes a batch
+//            of consecutive lines, loads their bit words at once, and thread j moves the batch's fresh pixel j
+//   expand   pixel -> result place cap - F + base[line] + rank in the line - 1, tiles of 32 channels x 64 rows through LDS,
+//            512-byte runs along the channels, non-temporal; a block walks up a column of tiles with a line's bit words in
+//            registers and the next tile's results in flight
 #include "gn_dedup.h"
 
 namespace dexct {
@@ -22,7 +24,7 @@ using namespace gn_dedup;
 
 constexpr int kBlock = 256, kWavesPerBlock = kBlock / kWave;
 constexpr int kMaxGrid = 2048;                   // the line and tile loops stride: a grid that returns at once stays cheap
-constexpr int kExpandC = 16, kExpandR = kWordBits;       // the expansion's tile: channels x rows
+constexpr int kExpandC = 32, kExpandR = kWordBits;       // the expansion's tile: channels x rows
 typedef double d2 __attribute__((ext_vector_type(2)));
 
 template <typename B> __device__ __forceinline__ B one_bits();
@@ -177,23 +179,55 @@ __global__ __launch_bounds__(kBlock) void gn_dedup_gather_kernel(const B* __rest
                                                                   const unsigned* __restrict__ bases, B* __restrict__ list1,
                                                                   B* __restrict__ list2) {
   if (desc[kDescUse] == 0ull) return;
+  static_assert(kGatherWords == kBlock, "a thread per word of a chunk");
+  __shared__ unsigned long long s_word[kGatherWords];
+  __shared__ uint32_t s_prefix[kGatherWords];
+  __shared__ unsigned s_wave[kWavesPerBlock];
   const long long n_fresh = (long long)desc[kDescFresh], cap = (long long)desc[kDescCap];
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, n_words = words_per_line(rows);
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, n_words = words_per_line(rows), batch = gather_batch_lines(rows);
   if (blockIdx.x == 0 && wv == 0) {                      // the places that share the first entry's tile
     const long long p = pad_begin(cap, n_fresh) + lane;
     if (p < pad_end(cap, n_fresh)) { list1[p] = one_bits<B>(); list2[p] = one_bits<B>(); }
   }
-  for (long long line = (long long)blockIdx.x * kWavesPerBlock + wv; line < n_lines; line += (long long)gridDim.x * kWavesPerBlock) {
-    const long long base = bases[line];
-    int before = 0;
-    for (int k = 0; k < n_words; ++k) {
-      const unsigned long long word = bits[word_index(line, rows, k)];
-      if ((word >> lane) & 1ull) {                       // (a set bit is a row of the line: the census sets no other)
-        const long long to = result_place(cap, n_fresh, base, rank_inclusive(before, word, lane)), from = line * rows + row_of(k, lane);
-        list1[to] = g1[from];
-        list2[to] = g2[from];
+  // The lines of a batch own consecutive places of the list, from list_place(base of the first line) on.  Every load of the
+  // index - the base, the bit words - is issued up front and unconditionally (a word beyond the batch reads the batch's last and
+  // counts as empty); the places then come from prefix sums of popcounts in LDS, so that thread j moves the chunk's fresh pixel j:
+  // neighbouring threads write neighbouring places, and no load of a value waits for more than the chunk's words.
+  for (long long b = blockIdx.x; b < gather_batches(n_lines, rows); b += gridDim.x) {
+    const long long line0 = b * batch, lines_here = n_lines - line0 < batch ? n_lines - line0 : batch;
+    const long long w_begin = line0 * n_words, n_here = lines_here * n_words;
+    long long run = list_place(cap, n_fresh, bases[line0]);
+    for (long long iw0 = 0; iw0 < n_here; iw0 += kGatherWords) {
+      const long long iw = iw0 + threadIdx.x;
+      unsigned long long word = bits[w_begin + (iw < n_here ? iw : n_here - 1)];
+      if (iw >= n_here) word = 0ull;
+      const unsigned mine = (unsigned)__popcll(word);
+      unsigned upto = mine;                              // inclusive scan over the wave, then over the block's waves
+#pragma unroll
+      for (int d = 1; d < kWave; d <<= 1) {
+        const unsigned y = __shfl_up(upto, d);
+        if (lane >= d) upto += y;
       }
-      before += (int)__popcll(word);
+      if (lane == kWave - 1) s_wave[wv] = upto;
+      __syncthreads();
+      unsigned waves_before = 0u, total = 0u;
+#pragma unroll
+      for (int k = 0; k < kWavesPerBlock; ++k) {
+        const unsigned c = s_wave[k];
+        if (k < wv) waves_before += c;
+        total += c;
+      }
+      s_word[threadIdx.x] = word;
+      s_prefix[threadIdx.x] = waves_before + upto - mine;
+      __syncthreads();
+      for (unsigned j = threadIdx.x; j < total; j += kBlock) {
+        const int i = word_of_fresh(s_prefix, kGatherWords, j);
+        const long long from = pixel_of_batch_word(line0, (int)iw0 + i, rows, select_bit(s_word[i], (int)(j - s_prefix[i])));
+        list1[run + j] = g1[from];
+        list2[run + j] = g2[from];
+      }
+      run += total;
+      __syncthreads();                                   // (the next chunk writes s_wave, s_word and s_prefix)
     }
   }
 }
@@ -210,6 +244,12 @@ __global__ void gn_dedup_direct_head_kernel(const unsigned long long* __restrict
   if (use) *progress = 0ull;                             // (the list's pixels; the expansion counts the sinograms')
 }
 
+// the word of lane `l` (the same l in every lane) of a value every lane holds one of
+__device__ __forceinline__ unsigned long long word_of_lane(unsigned long long x, int l) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)x, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(x >> 32), l);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
 __global__ __launch_bounds__(kBlock) void gn_dedup_expand_kernel(const unsigned long long* __restrict__ desc,
                                                                   const unsigned long long* __restrict__ bits,
                                                                   const unsigned* __restrict__ bases, const d2* __restrict__ results,
@@ -220,40 +260,55 @@ __global__ __launch_bounds__(kBlock) void gn_dedup_expand_kernel(const unsigned 
   const long long n_fresh = (long long)desc[kDescFresh], cap = (long long)desc[kDescCap];
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int tiles_r = words_per_line(rows), tiles_c = (channels + kExpandC - 1) / kExpandC;
-  constexpr int kPerWave = kExpandC / kWavesPerBlock;
+  constexpr int kPerWave = kExpandC / kWavesPerBlock, kRowsPerTrip = kBlock / kExpandC;
+  const int co = threadIdx.x % kExpandC, ro0 = threadIdx.x / kExpandC;
   unsigned long long written = 0ull;
-  // a block takes a COLUMN of tiles - 16 channels of a view, all rows - from the first row up: the fresh pixels of a line before
-  // the tile's word are then a running sum, not a loop over the earlier words
+  // a block takes a COLUMN of tiles - kExpandC channels of a view, all rows - from the first row up: the fresh pixels of a line
+  // before the tile's word are then a running sum, not a loop over the earlier words
   for (long long col = blockIdx.x; col < n_views * tiles_c; col += gridDim.x) {
-    const int cb = (int)(col % tiles_c);
+    const int cb = (int)(col % tiles_c), c = cb * kExpandC + co;
     const long long v = col / tiles_c;
     // (the loads below are unconditional - a channel beyond the last reads the last, a row beyond the line the line's last
-    // entry - so that the wave's four lines are in flight together)
+    // entry - so that all of a wave's lines are in flight together)
     long long line[kPerWave], base[kPerWave];
     int before[kPerWave];
+    unsigned long long words[kPerWave];                  // lane l: word rb0 + l of the line's bit row (rb0: a multiple of 64)
+    auto load_words = [&](int rb0) {
 #pragma unroll
-    for (int q = 0; q < kPerWave; ++q) {
-      const int c = cb * kExpandC + wv * kPerWave + q;
-      line[q] = v * channels + (c < channels ? c : channels - 1);
-      base[q] = bases[line[q]];
-      before[q] = 0;
-    }
-    for (int rb = 0; rb < tiles_r; ++rb) {
-      // in: a wave reads 64 rows of a line at a time (neighbouring lanes: the same or neighbouring entries of the results)
-      d2 val[kPerWave];
+      for (int q = 0; q < kPerWave; ++q) words[q] = bits[word_index(line[q], rows, rb0 + lane < tiles_r ? rb0 + lane : tiles_r - 1)];
+    };
+    // in: a wave reads 64 rows of a line at a time (neighbouring lanes: the same or neighbouring entries of the results); the
+    // place is arithmetic on registers
+    auto load_values = [&](int rb, d2* val) {
 #pragma unroll
       for (int q = 0; q < kPerWave; ++q) {
-        const unsigned long long word = bits[word_index(line[q], rows, rb)];
+        const unsigned long long word = word_of_lane(words[q], rb % kWave);
         val[q] = results[result_place(cap, n_fresh, base[q], rank_inclusive(before[q], word, lane))];
         before[q] += (int)__popcll(word);
       }
+    };
+#pragma unroll
+    for (int q = 0; q < kPerWave; ++q) {
+      const int cq = cb * kExpandC + wv * kPerWave + q;
+      line[q] = v * channels + (cq < channels ? cq : channels - 1);
+      base[q] = bases[line[q]];
+      before[q] = 0;
+    }
+    load_words(0);
+    d2 val[kPerWave];
+    load_values(0, val);
+    for (int rb = 0; rb < tiles_r; ++rb) {
 #pragma unroll
       for (int q = 0; q < kPerWave; ++q) tile[wv * kPerWave + q][lane] = val[q];
+      if (rb + 1 < tiles_r) {                            // the next tile's values travel, into registers, while this one is written out
+        if ((rb + 1) % kWave == 0) load_words(rb + 1);
+        load_values(rb + 1, val);
+      }
       __syncthreads();
-      // out: 16 lanes write the 16 channels of a row, 256 bytes
-      const int co = threadIdx.x % kExpandC, c = cb * kExpandC + co;
-      for (int k = 0; k < kExpandR / (kBlock / kExpandC); ++k) {
-        const int ro = threadIdx.x / kExpandC + k * (kBlock / kExpandC), r = row_of(rb, ro);
+      // out: kExpandC lanes write the channels of a row, one run
+#pragma unroll
+      for (int k = 0; k < kExpandR / kRowsPerTrip; ++k) {
+        const int ro = ro0 + k * kRowsPerTrip, r = row_of(rb, ro);
         if (c < channels && r < rows) __builtin_nontemporal_store(tile[co][ro], out_a + ((v * rows + r) * channels + c));
       }
       __syncthreads();
@@ -294,7 +349,7 @@ int prepare(const GnDedupCall& dc, const void* g1v, const void* g2v, hipStream_t
   hipLaunchKernelGGL(gn_dedup_bases_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, st, (const unsigned*)counts, (long long)y.n_lines,
                      (const unsigned long long*)desc, (const unsigned*)sums, bases);
   DEXCT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(gn_dedup_gather_kernel<B>, dim3(capped_grid(line_blocks)), dim3(kBlock), 0, st, g1, g2, (long long)y.n_lines, dc.rows,
+  hipLaunchKernelGGL(gn_dedup_gather_kernel<B>, dim3(capped_grid(gather_batches(y.n_lines, dc.rows))), dim3(kBlock), 0, st, g1, g2, (long long)y.n_lines, dc.rows,
                      (const unsigned long long*)desc, (const unsigned long long*)bits, (const unsigned*)bases, dc.array<B>(y.list1),
                      dc.array<B>(y.list2));
   DEXCT_LAUNCH_CHECK();

@@ -62,6 +62,40 @@ DEXCT_GN_DEDUP_HD int rank_inclusive(int before, uint64_t word, int bit) { retur
 // the entry of the result array a pixel takes: base = fresh pixels of all earlier lines, rank = rank_inclusive >= 1
 DEXCT_GN_DEDUP_HD int64_t result_place(int64_t cap, int64_t n_fresh, int64_t base, int rank) { return cap - n_fresh + base + rank - 1; }
 
+// ---- the gather's batches -------------------------------------------------------------------------------------------------------
+// A block of the gather takes a BATCH of consecutive lines: as many whole lines as have kGatherWords bit words between them (one
+// line where a line alone has more), and works through the batch's words in chunks of kGatherWords.  The fresh pixels of a chunk
+// are numbered j = 0, 1, ... in the order of the pixels; pixel j's word is found in the exclusive prefix sums of the words'
+// popcounts, its bit by its rank within the word.
+constexpr int kGatherWords = 256;
+DEXCT_GN_DEDUP_HD int gather_batch_lines(int rows) { return words_per_line(rows) >= kGatherWords ? 1 : kGatherWords / words_per_line(rows); }
+DEXCT_GN_DEDUP_HD int64_t gather_batches(int64_t n_lines, int rows) { return (n_lines + gather_batch_lines(rows) - 1) / gather_batch_lines(rows); }
+// the last of the n (a power of two) words whose exclusive prefix is <= j: the word that holds fresh pixel j < the chunk's total
+// (words without a fresh pixel share their prefix with the word after them, so the last such word is never one of them)
+DEXCT_GN_DEDUP_HD int word_of_fresh(const uint32_t* prefix, int n, uint32_t j) {
+  int i = 0;
+  for (int step = n >> 1; step >= 1; step >>= 1)
+    if (prefix[i + step] <= j) i += step;
+  return i;
+}
+// the bit of the k-th set bit of `word`, k = 0 the lowest (k < popcount(word))
+DEXCT_GN_DEDUP_HD int select_bit(uint64_t word, int k) {
+  int bit = 0;
+  for (int half = kWordBits / 2; half >= 1; half >>= 1) {
+    const int low = __builtin_popcountll(word & ((uint64_t(1) << half) - 1u));
+    if (k >= low) {
+      k -= low;
+      word >>= half;
+      bit += half;
+    }
+  }
+  return bit;
+}
+// the pixel of bit `bit` of the batch's word iw (0 = word 0 of the batch's first line, line0)
+DEXCT_GN_DEDUP_HD int64_t pixel_of_batch_word(int64_t line0, int iw, int rows, int bit) {
+  return (line0 + iw / words_per_line(rows)) * rows + row_of(iw % words_per_line(rows), bit);
+}
+
 // ---- the workspace: descriptor | bits | counts | bases | block sums of the scan | list of g1 | list of g2 | results ---------------
 struct Layout {
   int64_t n_lines, cap;
