@@ -211,6 +211,12 @@ def _dual_energy_shard(n, n_views, n_channels, view_range, sample_views, rows_at
         R, C = int(counts.shape[3]), int(counts.shape[2])
         a_ref = md.gn_device(counts[0], counts[1], i0, mus, n_iters, 'f64', mask_max=gmax, mask_frac=0.95, out_rc=(R, C))
         assert a_ref.shape == (V, R, C, 2)
+        # which route that call took (the default: the dedup route at this size): the descriptor, against the rules of
+        # include/dexct_gn_dedup.h applied to the counts on the device
+        import gn_dedup_caps
+        dd, dd_want = md.last_gn_stats()['dedup'], gn_dedup_caps.device_expected(counts)
+        print(f'dedup route of the out_rc call: {dd}, expected {dd_want}')
+        assert dd == dd_want, (dd, dd_want)
         for v0 in range(0, V, 100):
             assert torch.equal(a_ref[v0:v0 + 100].view(torch.int64),
                                a[v0:v0 + 100].permute(0, 2, 1, 3).contiguous().view(torch.int64))
