@@ -14,8 +14,8 @@ input/params.txt:24) down to pi + the fan angle are reconstructed with Parker's 
 import numpy as np
 import torch
 
-from . import _native, xcompy
-from ._device import device, ptr, stream_ptr, to_dev
+from . import _native, iterative, xcompy
+from ._device import device, ptr, stream_ptr, to_dev, to_host
 from .forward_project import effective_weights
 
 WATER = 'H(11.2)O(88.8)'       # the composition plots.py:140 uses for HU
@@ -35,6 +35,16 @@ def default_window():
     the plain band-limited ramp stays the default and the window is a choice (``DEXCT_FBP_WINDOW``)."""
     import os
     return os.environ.get('DEXCT_FBP_WINDOW', 'rect')
+
+
+def _window(window, default=True):
+    """The name of the ramp's window: ``default_window()`` where the caller named none (unless ``default`` is off), a ValueError
+    for a name WINDOWS does not have."""
+    if default:
+        window = window or default_window()
+    if window not in WINDOWS:
+        raise ValueError(f'unknown filter window {window!r}; choose from {sorted(WINDOWS)}')
+    return window
 
 
 def _windowed_ramp(t, fc, window):
@@ -57,8 +67,7 @@ def _windowed_ramp(t, fc, window):
 def ramp_taps(n_channels, dgamma, ramp=1.0, window='rect'):
     """Equiangular filter taps g(n dgamma), n = -(N-1)..(N-1), cutoff ``ramp`` x Nyquist (float64);
     ``window`` apodises the ramp below the cutoff (WINDOWS)."""
-    if window not in WINDOWS:
-        raise ValueError(f'unknown filter window {window!r}; choose from {sorted(WINDOWS)}')
+    window = _window(window, default=False)
     n = np.arange(-(n_channels - 1), n_channels, dtype=np.float64)
     c = float(ramp)
     t = n * dgamma
@@ -98,19 +107,68 @@ def _short_scan(ct):
     return True
 
 
-def _fbp_inputs(ct, ramp, window, cone, slices, dtype, dev):
-    """What the filter and the back-projection read besides the sinogram, on the device: the taps and the channel weight
-    SID cos(gamma) in ``dtype`` (float32 for the image, float64 for its covariance), (cos, sin) of the views in float64 and,
-    for a cone, ``(row weights in dtype, z of row 0, n_slices, z0, dz)`` - else None."""
-    taps = to_dev(ramp_taps(ct.N_channels, ct.dgamma, ramp, window), dtype, dev)
+def _check_sino_shape(shape, ct, what='sinogram', tail=0):
+    """[N_proj, N_channels] or [N_proj, N_rows, N_channels] of the scanner, and ``tail`` more axes (the planes of a covariance)."""
+    shape = tuple(shape)
+    if len(shape) - tail not in (2, 3) or shape[0] != ct.N_proj or shape[-1 - tail] != ct.N_channels:
+        raise ValueError(f'{what} {shape} does not match the scanner ({ct.N_proj} x {ct.N_channels})')
+
+
+def _single_process(caller):
+    from . import _shard
+    if _shard.world()[1] > 1:
+        raise NotImplementedError(f'{caller} runs on a single process')
+
+
+def _stack(t, tail=0):
+    """The lift of [views, channels(, T)] to the stack [views, 1, channels(, T)] the kernels take; a stack stays as it is.
+    Returns it contiguous, and ``back``: what takes the lift off an image stack again (img -> img[0], or nothing)."""
+    if t.dim() - tail == 3:
+        return t.contiguous(), lambda img: img
+    return t[(slice(None), None) + (slice(None),) * (1 + tail)].contiguous(), lambda img: img[0]          # t[:, None, :(, :)]
+
+
+def _zero_nonfinite(t, caller, what):
+    """The non-finite rule of every reconstruction entry point: count, warn (``caller: n non-finite <what>``), set to 0.
+    Returns the cleaned tensor and the mask of the finite values - None where every value is finite."""
+    finite = torch.isfinite(t)
+    bad = int((~finite).sum().item())
+    if not bad:
+        return t, None
+    # one NaN (a photon-starved ray whose decomposition diverged, ln of a zero count) would spread over its whole
+    # detector line in the filter and over the whole image in the back-projection
+    import warnings
+    warnings.warn(f'{caller}: {bad} non-finite {what}', RuntimeWarning, stacklevel=2)
+    return torch.nan_to_num(t, nan=0.0, posinf=0.0, neginf=0.0), finite
+
+
+def _cone(ct, n_rows, what='sinogram'):
+    """Does a stack of ``n_rows`` rows go through Feldkamp's algorithm: a cone-beam scanner and more than one row - which
+    then must be the scanner's rows."""
+    cone = bool(getattr(ct, 'cone', False)) and n_rows > 1
+    if cone and n_rows != ct.N_rows:
+        raise ValueError(f'{what} has {n_rows} rows, the scanner {ct.N_rows}')
+    return cone
+
+
+def _fbp_inputs(s, ct, what, N_matrix, FOV, ramp, window, slices):
+    """What the filter and the back-projection read besides the stack ``s``, on its device: the taps and the channel weight
+    SID cos(gamma) in its dtype (float32 for the image, float64 for its covariance), (cos, sin) of the views in float64, the row
+    weights of a cone in its dtype (None for a fan: _cone decides, ``what`` names ``s`` if it refuses), the number of images, and
+    the scanner geometry: the arguments that follow the counts in the call of the fan or the Feldkamp back-projection."""
+    n_rows, dtype, dev = s.shape[1], s.dtype, s.device
+    cone = _cone(ct, n_rows, what)
+    taps = to_dev(ramp_taps(ct.N_channels, ct.dgamma, ramp, _window(window)), dtype, dev)
     weight = to_dev(ct.SID * np.cos(ct.gammas), dtype, dev)
     view_cs = to_dev(ct.view_cs(), torch.float64, dev)
+    dtheta, grid = ct.theta_tot / ct.N_proj, (int(N_matrix), float(FOV))
     if not cone:
-        return taps, weight, view_cs, None
+        return taps, weight, view_cs, None, n_rows, (ct.SID, ct.dgamma, dtheta) + grid
     n_slices, z0, dz = slices if slices is not None else default_slices(ct)
     row_z = ct.row_z()
     row_w = to_dev(ct.SDD / np.sqrt(ct.SDD ** 2 + (row_z - ct.src_z) ** 2), dtype, dev)
-    return taps, weight, view_cs, (row_w, float(row_z[0]), int(n_slices), float(z0), float(dz))
+    return taps, weight, view_cs, row_w, int(n_slices), (ct.SID, ct.SDD, ct.dgamma, dtheta, float(row_z[0]), float(ct.h),
+                                                         float(ct.src_z)) + grid + (int(n_slices), float(z0), float(dz))
 
 
 def recon_device(sino_d, ct, N_matrix, FOV, ramp, window=None, slices=None, bhc=None, method='fbp', n_iters=20, n_subsets=1,
@@ -120,64 +178,48 @@ def recon_device(sino_d, ct, N_matrix, FOV, ramp, window=None, slices=None, bhc=
     reconstructed with Feldkamp's algorithm onto ``slices = (n_slices, z_first [cm], dz [cm])``.  ``bhc``: a
     ``bhc.LinearizationTable`` - the sinogram is linearised first (into a new buffer; sino_d is left as it is), before
     Parker's weights, which a nonlinear map must not follow.  ``method`` and the keywords after it: see get_recon."""
+    n_subsets = iterative.check_options(method, ct, n_iters, n_subsets, relax, init)
     if method != 'fbp':
-        return _recon_iterative(sino_d, ct, N_matrix, FOV, ramp, window, bhc, method, n_iters, n_subsets, relax, init, nonneg,
-                                history)
+        return _recon_sirt(sino_d, ct, N_matrix, FOV, ramp, window, bhc, n_iters, n_subsets, relax, init, nonneg, history)
     lib = _native.load()
-    dev = sino_d.device
-    three_d = sino_d.dim() == 3
-    s = sino_d if three_d else sino_d[:, None, :]
-    s = s.contiguous()
+    s, back = _stack(sino_d)
     if bhc is not None:
         from .bhc import linearize_device
         s = linearize_device(s, bhc)
     n_views, n_rows, n_ch = s.shape
-    if n_views != ct.N_proj or n_ch != ct.N_channels:
-        raise ValueError(f'sinogram {tuple(sino_d.shape)} does not match the scanner ({ct.N_proj} x {ct.N_channels})')
+    _check_sino_shape(sino_d.shape, ct)
     st = stream_ptr()
     if _short_scan(ct):
         sw = torch.empty_like(s)
         _native.check(lib.dexct_fbp_parker(ptr(s), n_views, n_rows, n_ch, float(ct.theta_tot), float(ct.dgamma), 0, n_views,
                                            ptr(sw), st), 'dexct_fbp_parker')
         s = sw
-    cone = bool(getattr(ct, 'cone', False)) and n_rows > 1
-    if cone and n_rows != ct.N_rows:
-        raise ValueError(f'sinogram has {n_rows} rows, the scanner {ct.N_rows}')
-    taps, weight, view_cs, fdk = _fbp_inputs(ct, ramp, window or default_window(), cone, slices, torch.float32, dev)
+    taps, weight, view_cs, row_w, n_images, geometry = _fbp_inputs(s, ct, 'sinogram', N_matrix, FOV, ramp, window, slices)
     q = torch.empty_like(s)
     _native.check(lib.dexct_fbp_filter(ptr(s), ptr(taps), ptr(weight), n_views * n_rows, n_ch, ct.dgamma, ptr(q), st),
                   'dexct_fbp_filter')
-    if cone:
-        row_w, row_z0, n_slices, z0, dz = fdk
-        img = torch.empty((n_slices, N_matrix, N_matrix), dtype=torch.float32, device=dev)
-        _native.check(lib.dexct_fdk_backproject(ptr(q), ptr(view_cs), ptr(row_w), n_views, n_ch, n_rows, ct.SID, ct.SDD,
-                                                ct.dgamma, ct.theta_tot / ct.N_proj, row_z0, float(ct.h), float(ct.src_z),
-                                                int(N_matrix), float(FOV), n_slices, z0, dz, ptr(img), st),
+    img = torch.empty((n_images, N_matrix, N_matrix), dtype=torch.float32, device=s.device)
+    if row_w is not None:
+        _native.check(lib.dexct_fdk_backproject(ptr(q), ptr(view_cs), ptr(row_w), n_views, n_ch, n_rows, *geometry, ptr(img), st),
                       'dexct_fdk_backproject')
         return img
-    img = torch.empty((n_rows, N_matrix, N_matrix), dtype=torch.float32, device=dev)
-    _native.check(lib.dexct_fbp_backproject(ptr(q), ptr(view_cs), n_views, n_ch, n_rows, ct.SID, ct.dgamma,
-                                            ct.theta_tot / ct.N_proj, int(N_matrix), float(FOV), ptr(img), st),
+    _native.check(lib.dexct_fbp_backproject(ptr(q), ptr(view_cs), n_views, n_ch, n_rows, *geometry, ptr(img), st),
                   'dexct_fbp_backproject')
-    return img if three_d else img[0]
+    return back(img)
 
 
-def _recon_iterative(sino_d, ct, N_matrix, FOV, ramp, window, bhc, method, n_iters, n_subsets, relax, init, nonneg, history):
-    """SIRT / OS-SART of a fan or stacked-fan sinogram (iterative.py), from the FBP image or from zero."""
-    from . import iterative
-    n_subsets = iterative.check_options(method, ct, n_iters, n_subsets, relax, init)
-    three_d = sino_d.dim() == 3
-    s = (sino_d if three_d else sino_d[:, None, :]).contiguous()
+def _recon_sirt(sino_d, ct, N_matrix, FOV, ramp, window, bhc, n_iters, n_subsets, relax, init, nonneg, history):
+    """SIRT / OS-SART of a fan or stacked-fan sinogram (iterative.sirt), from the FBP image or from zero; the options have
+    passed iterative.check_options.  ``bhc`` as for recon_device: a table, applied into a new buffer."""
+    s, back = _stack(sino_d)
     n_views, n_rows, n_ch = s.shape
-    if n_views != ct.N_proj or n_ch != ct.N_channels:
-        raise ValueError(f'sinogram {tuple(sino_d.shape)} does not match the scanner ({ct.N_proj} x {ct.N_channels})')
+    _check_sino_shape(sino_d.shape, ct)
     proj = iterative.ImageProjector(ct, N_matrix, FOV, n_slices=n_rows)
     if bhc is not None:
         from .bhc import linearize_device
         s = linearize_device(s, bhc)
     x0 = recon_device(s, ct, N_matrix, FOV, ramp, window) if init == 'fbp' else None
-    img = iterative.sirt(s, proj, n_iters, n_subsets, relax, x0=x0, nonneg=nonneg, history=history)
-    return img if three_d else img[0]
+    return back(iterative.sirt(s, proj, n_iters, n_subsets, relax, x0=x0, nonneg=nonneg, history=history))
 
 
 def get_recon(sino, ct, spec, N_matrix, FOV, ramp, window=None, slices=None, bhc=None, method='fbp', n_iters=20, n_subsets=1,
@@ -202,9 +244,8 @@ def get_recon(sino, ct, spec, N_matrix, FOV, ramp, window=None, slices=None, bhc
     ``history`` (here: the objective before each iteration) as above, ``relax`` is not used.  Non-finite sinogram values get
     the weight 0.  Like ``sino``, ``weights`` is a host array (device tensors: iterative.pwls); ``slices`` belongs to the cone
     branch and is refused here; single process, as get_basismat_recon."""
-    pwls = method == 'pwls'
-    if pwls:
-        from . import iterative
+    # host checks: nothing here touches the device
+    if method == 'pwls':
         n_subsets, beta, delta = iterative.check_pwls_options(ct, 1, n_iters, n_subsets, beta, delta, init, FOV)
         if weights is None:
             raise ValueError("method='pwls' needs weights: the inverse variance of every sinogram value")
@@ -214,46 +255,33 @@ def get_recon(sino, ct, spec, N_matrix, FOV, ramp, window=None, slices=None, bhc
             raise ValueError('get_recon takes host arrays: device tensors go to get_basismat_recon or iterative.pwls')
         if tuple(np.shape(weights)) != tuple(np.shape(sino)):
             raise ValueError(f'weights {tuple(np.shape(weights))} do not have the shape of the sinogram {tuple(np.shape(sino))}')
-        if np.ndim(sino) not in (2, 3) or np.shape(sino)[0] != ct.N_proj or np.shape(sino)[-1] != ct.N_channels:
-            raise ValueError(f'sinogram {tuple(np.shape(sino))} does not match the scanner ({ct.N_proj} x {ct.N_channels})')
-        from . import _shard
-        if _shard.world()[1] > 1:
-            raise NotImplementedError("get_recon(method='pwls') runs on a single process")
+        _check_sino_shape(np.shape(sino), ct)
+        _single_process("get_recon(method='pwls')")
     elif weights is not None:
         raise ValueError(f"weights belong to method='pwls', not to {method!r}")
-    elif method != 'fbp':
-        from . import iterative
-        iterative.check_options(method, ct, n_iters, n_subsets, relax, init, FOV)
-    dev = device()
-    sino_d = to_dev(np.asarray(sino, dtype=np.float32), torch.float32, dev)
-    bad = int((~torch.isfinite(sino_d)).sum().item())
-    if bad:
-        # one NaN (a photon-starved ray whose decomposition diverged, ln of a zero count) would spread over its whole
-        # detector line in the filter and over the whole image in the back-projection
-        import warnings
-        warnings.warn(f'get_recon: {bad} non-finite sinogram value(s) set to 0 before filtering', RuntimeWarning)
-        dead = ~torch.isfinite(sino_d) if pwls else None
-        sino_d = torch.nan_to_num(sino_d, nan=0.0, posinf=0.0, neginf=0.0)
+    else:
+        n_subsets = iterative.check_options(method, ct, n_iters, n_subsets, relax, init, FOV)
+    sino_d = to_dev(np.asarray(sino, dtype=np.float32), torch.float32, device())
+    sino_d, finite = _zero_nonfinite(sino_d, 'get_recon', 'sinogram value(s) set to 0 before filtering')
     if bhc is not None:
         from . import bhc as bhc_mod
         table = bhc if isinstance(bhc, bhc_mod.LinearizationTable) else bhc_mod.linearization_table(ct, spec, bhc)
         bhc_mod.linearize_device(sino_d, table, out=sino_d)         # sino_d is this call's own copy
-    if pwls:
-        weights_d = to_dev(np.asarray(weights, dtype=np.float32), torch.float32, dev)
+    if method == 'pwls':
+        weights_d = to_dev(np.asarray(weights, dtype=np.float32), torch.float32, sino_d.device)
         if not bool((torch.isfinite(weights_d) & (weights_d >= 0)).all().item()):
             raise ValueError('weights must be finite and >= 0')
-        if bad:
-            weights_d[dead] = 0.0
-        three_d = sino_d.dim() == 3
-        shape = (1, ct.N_proj, sino_d.shape[1] if three_d else 1, ct.N_channels)
-        img = _recon_pwls(sino_d.reshape(shape), weights_d.reshape(shape), ct, N_matrix, FOV, ramp, window, beta, delta, n_iters,
-                          n_subsets, init, nonneg, history)[0]
-        raw = (img if three_d else img[0]).cpu().numpy()
-    elif method != 'fbp':
-        raw = recon_device(sino_d, ct, N_matrix, FOV, ramp, window, None, None, method, n_iters, n_subsets, relax, init, nonneg,
-                           history).cpu().numpy()
+        if finite is not None:
+            weights_d[~finite] = 0.0
+        s, back = _stack(sino_d)
+        img = back(_recon_pwls(s[None], weights_d.reshape((1,) + s.shape), ct, N_matrix, FOV, ramp, window, beta, delta, n_iters,
+                               n_subsets, init, nonneg, history)[0])
+    elif method == 'fbp':
+        img = recon_device(sino_d, ct, N_matrix, FOV, ramp, window=window, slices=slices)
     else:
-        raw = recon_device(sino_d, ct, N_matrix, FOV, ramp, window, slices).cpu().numpy()
+        img = _recon_sirt(sino_d, ct, N_matrix, FOV, ramp, window, bhc=None, n_iters=n_iters, n_subsets=n_subsets, relax=relax,
+                          init=init, nonneg=nonneg, history=history)
+    raw = img.cpu().numpy()
     mu_w = water_mu(ct, spec)
     return raw, (1000.0 * (raw - mu_w) / mu_w).astype(np.float32)
 
@@ -261,12 +289,9 @@ def get_recon(sino, ct, spec, N_matrix, FOV, ramp, window=None, slices=None, bhc
 def _recon_pwls(sinos_d, weights_d, ct, N_matrix, FOV, ramp, window, beta, delta, n_iters, n_subsets, init, nonneg, history):
     """iterative.pwls of sinograms [K, N_proj, n_rows, N_channels] with the packed weights [T, N_proj, n_rows, N_channels]
     (device float32), every channel started from its FBP image (``init='fbp'``) or from zero -> images [K, n_rows, N, N]."""
-    from . import iterative
     K, _, n_rows, _ = sinos_d.shape
     proj = iterative.ImageProjector(ct, N_matrix, FOV, n_slices=n_rows)
-    x0 = None
-    if init == 'fbp':
-        x0 = torch.stack([recon_device(sinos_d[k], ct, N_matrix, FOV, ramp, window) for k in range(K)])
+    x0 = torch.stack([recon_device(sinos_d[k], ct, N_matrix, FOV, ramp, window) for k in range(K)]) if init == 'fbp' else None
     return iterative.pwls(sinos_d, weights_d, proj, n_iters, n_subsets, beta, delta, x0=x0, nonneg=nonneg, history=history)
 
 
@@ -287,7 +312,6 @@ def get_basismat_recon(basis_sinos, cov_sino, ct, N_matrix, FOV, ramp, beta, del
     ``history``: a list that receives the objective before each iteration.  Returns a tuple of K images [N_matrix, N_matrix]
     or [N_rows, N_matrix, N_matrix], float32: NumPy arrays, or device tensors if the sinograms were device tensors.  Fan and
     stacked fan only; single process."""
-    from . import iterative
     sinos = list(basis_sinos)
     K = len(sinos)
     n_subsets, beta, delta = iterative.check_pwls_options(ct, K, n_iters, n_subsets, beta, delta, init, FOV)
@@ -295,40 +319,28 @@ def get_basismat_recon(basis_sinos, cov_sino, ct, N_matrix, FOV, ramp, beta, del
     shape = shapes[0]
     if any(sh != shape for sh in shapes):
         raise ValueError(f'the basis sinograms differ in shape: {shapes}')
-    if len(shape) not in (2, 3) or shape[0] != ct.N_proj or shape[-1] != ct.N_channels:
-        raise ValueError(f'sinogram {shape} does not match the scanner ({ct.N_proj} x {ct.N_channels})')
+    _check_sino_shape(shape, ct)
     T = K * (K + 1) // 2
     cov_shape = tuple(cov_sino.shape) if isinstance(cov_sino, torch.Tensor) else np.shape(cov_sino)
     if cov_shape != shape + (T,):
         raise ValueError(f'covariance sinogram {cov_shape}: {shape + (T,)} wanted for {K} sinogram(s) of shape {shape}')
-    if not (float(w_fill) >= 0.0 and np.isfinite(float(w_fill))):
-        raise ValueError(f'w_fill = {w_fill}: a finite value >= 0 wanted')
-    window = window or default_window()
-    if window not in WINDOWS:
-        raise ValueError(f'unknown filter window {window!r}; choose from {sorted(WINDOWS)}')
+    iterative.check_w_fill(w_fill)
+    window = _window(window)
     _short_scan(ct)
-    from . import _shard
-    if _shard.world()[1] > 1:
-        raise NotImplementedError('get_basismat_recon runs on a single process')
+    _single_process('get_basismat_recon')
     tensors_in = all(isinstance(t, torch.Tensor) for t in sinos)
     dev = device()
-    three_d = len(shape) == 3
-    full = (ct.N_proj, shape[1] if three_d else 1, ct.N_channels)
-    s = torch.stack([to_dev(t if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float32), torch.float32, dev).reshape(full)
-                     for t in sinos])
+    stacks = [_stack(to_dev(t if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float32), torch.float32, dev)) for t in sinos]
+    s, back = torch.stack([st for st, _ in stacks]), stacks[0][1]
     cov_d = to_dev(cov_sino if isinstance(cov_sino, torch.Tensor) else np.asarray(cov_sino, dtype=np.float64), torch.float64, dev)
-    cov_d = cov_d.reshape(full + (T,))
-    finite = torch.isfinite(s)
-    bad = int((~finite).sum().item())
-    if bad:
-        import warnings
-        warnings.warn(f'get_basismat_recon: {bad} non-finite sinogram value(s) set to 0 before the reconstruction', RuntimeWarning)
-        s = torch.nan_to_num(s, nan=0.0, posinf=0.0, neginf=0.0)
+    cov_d = _stack(cov_d, tail=1)[0]
+    s, finite = _zero_nonfinite(s, 'get_basismat_recon', 'sinogram value(s) set to 0 before the reconstruction')
+    if finite is not None:
         # their rays are unusable: a NaN covariance makes dexct_cov_precision write w_fill (into a copy: cov_sino is the caller's)
         cov_d = torch.where(finite.all(0)[..., None], cov_d, torch.full_like(cov_d, float('nan')))
     w = iterative.precision_weights(cov_d, w_fill)
     imgs = _recon_pwls(s, w, ct, N_matrix, FOV, ramp, window, beta, delta, n_iters, n_subsets, init, nonneg, history)
-    out = tuple(imgs[k] if three_d else imgs[k, 0] for k in range(K))
+    out = tuple(back(imgs[k]) for k in range(K))
     return out if tensors_in else tuple(t.cpu().numpy() for t in out)
 
 
@@ -340,16 +352,12 @@ def _check_cov_sino(shape, ct, window):
         raise ValueError(f'covariance sinogram {shape} has no plane axis: pass a single variance sinogram as var[..., None]')
     if len(shape) not in (3, 4):
         raise ValueError(f'covariance sinogram must be [N_proj, N_channels, T] or [N_proj, N_rows, N_channels, T], got {shape}')
-    if shape[0] != ct.N_proj or shape[-2] != ct.N_channels:
-        raise ValueError(f'covariance sinogram {shape} does not match the scanner ({ct.N_proj} x {ct.N_channels})')
+    _check_sino_shape(shape, ct, 'covariance sinogram', tail=1)
     if shape[-1] < 1:
         raise ValueError('covariance sinogram has no planes')
-    window = window or default_window()
-    if window not in WINDOWS:
-        raise ValueError(f'unknown filter window {window!r}; choose from {sorted(WINDOWS)}')
+    window = _window(window)
     _short_scan(ct)
-    if bool(getattr(ct, 'cone', False)) and len(shape) == 4 and shape[1] > 1 and shape[1] != ct.N_rows:
-        raise ValueError(f'covariance sinogram has {shape[1]} rows, the scanner {ct.N_rows}')
+    _cone(ct, shape[1] if len(shape) == 4 else 1, 'covariance sinogram')
     if ct.N_channels > _native.FBP_VAR_MAX_CHANNELS:
         raise ValueError(f'{ct.N_channels} channels: the variance filter takes at most {_native.FBP_VAR_MAX_CHANNELS}')
     return window
@@ -367,31 +375,22 @@ def recon_covariance_device(cov_d, ct, N_matrix, FOV, ramp, window=None, slices=
         raise ValueError('cov_d must be a float64 device tensor')
     window = _check_cov_sino(cov_d.shape, ct, window)
     lib = _native.load()
-    dev = cov_d.device
-    four_d = cov_d.dim() == 4
-    s = (cov_d if four_d else cov_d[:, None, :, :]).contiguous()
+    s, back = _stack(cov_d, tail=1)
     n_views, n_rows, n_ch, n_planes = s.shape
     st = stream_ptr()
-    short = _short_scan(ct)
-    cone = bool(getattr(ct, 'cone', False)) and n_rows > 1
-    taps, weight, view_cs, fdk = _fbp_inputs(ct, ramp, window, cone, slices, torch.float64, dev)
+    taps, weight, view_cs, row_w, n_images, geometry = _fbp_inputs(s, ct, 'covariance sinogram', N_matrix, FOV, ramp, window, slices)
     qa, qb = torch.empty_like(s), torch.empty_like(s)
     _native.check(lib.dexct_fbp_var_filter(ptr(s), n_views, n_rows, n_ch, n_planes, ptr(taps), ptr(weight), float(ct.dgamma),
-                                           float(ct.theta_tot) if short else 2 * np.pi, 0, n_views, ptr(qa), ptr(qb), st),
+                                           float(ct.theta_tot) if _short_scan(ct) else 2 * np.pi, 0, n_views, ptr(qa), ptr(qb), st),
                   'dexct_fbp_var_filter')
-    if cone:
-        row_w, row_z0, n_slices, z0, dz = fdk
-        img = torch.empty((n_slices, N_matrix, N_matrix, n_planes), dtype=torch.float64, device=dev)
+    img = torch.empty((n_images, N_matrix, N_matrix, n_planes), dtype=torch.float64, device=s.device)
+    if row_w is not None:
         _native.check(lib.dexct_fdk_var_backproject(ptr(qa), ptr(qb), ptr(view_cs), ptr(row_w), n_views, n_ch, n_rows, n_planes,
-                                                    ct.SID, ct.SDD, ct.dgamma, ct.theta_tot / ct.N_proj, row_z0, float(ct.h),
-                                                    float(ct.src_z), int(N_matrix), float(FOV), n_slices, z0, dz, ptr(img), st),
-                      'dexct_fdk_var_backproject')
+                                                    *geometry, ptr(img), st), 'dexct_fdk_var_backproject')
         return img
-    img = torch.empty((n_rows, N_matrix, N_matrix, n_planes), dtype=torch.float64, device=dev)
-    _native.check(lib.dexct_fbp_var_backproject(ptr(qa), ptr(qb), ptr(view_cs), n_views, n_ch, n_rows, n_planes, ct.SID, ct.dgamma,
-                                                ct.theta_tot / ct.N_proj, int(N_matrix), float(FOV), ptr(img), st),
-                  'dexct_fbp_var_backproject')
-    return img if four_d else img[0]
+    _native.check(lib.dexct_fbp_var_backproject(ptr(qa), ptr(qb), ptr(view_cs), n_views, n_ch, n_rows, n_planes, *geometry, ptr(img),
+                                                st), 'dexct_fbp_var_backproject')
+    return back(img)
 
 
 def get_recon_covariance(cov_sino, ct, N_matrix, FOV, ramp, window=None, slices=None):
@@ -403,19 +402,11 @@ def get_recon_covariance(cov_sino, ct, N_matrix, FOV, ramp, window=None, slices=
     decomposition) are set to 0 with a RuntimeWarning - get_recon's rule: they must not smear over the image.  Sinogram
     pixels are taken as independent; the result is the pixel-wise (co)variance of the FBP image (recon_covariance_device).
     NumPy in -> NumPy out; a device tensor in -> a device tensor out.  Single process only."""
-    from . import _shard
-    from ._device import to_host
     tensor_in = isinstance(cov_sino, torch.Tensor)
     window = _check_cov_sino(cov_sino.shape if tensor_in else np.shape(cov_sino), ct, window)
-    if _shard.world()[1] > 1:
-        raise NotImplementedError('get_recon_covariance runs on a single process')
-    dev = device()
-    cov_d = to_dev(cov_sino if tensor_in else np.asarray(cov_sino, dtype=np.float64), torch.float64, dev)
-    bad = int((~torch.isfinite(cov_d)).sum().item())
-    if bad:
-        import warnings
-        warnings.warn(f'get_recon_covariance: {bad} non-finite covariance value(s) set to 0 before filtering', RuntimeWarning)
-        cov_d = torch.nan_to_num(cov_d, nan=0.0, posinf=0.0, neginf=0.0)
+    _single_process('get_recon_covariance')
+    cov_d = to_dev(cov_sino if tensor_in else np.asarray(cov_sino, dtype=np.float64), torch.float64, device())
+    cov_d, _ = _zero_nonfinite(cov_d, 'get_recon_covariance', 'covariance value(s) set to 0 before filtering')
     out = recon_covariance_device(cov_d, ct, N_matrix, FOV, ramp, window, slices)
     return out if tensor_in else to_host(out)
 

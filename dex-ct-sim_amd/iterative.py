@@ -39,12 +39,8 @@ METHODS = ('fbp', 'sirt', 'os-sart')
 OS_SART_SUBSETS = 10
 
 
-def check_options(method, ct, n_iters, n_subsets, relax, init='fbp', FOV=None):
-    """The argument checks of ``get_recon(..., method=)``, before any device access.  Returns the subset count."""
-    if method not in METHODS:
-        raise ValueError(f'unknown reconstruction method {method!r}; choose from {METHODS}')
-    if method == 'fbp':
-        return 1
+def _check_iteration(ct, FOV, init, n_iters):
+    """What check_options and check_pwls_options ask alike, up to the iteration count; _check_subsets closes both."""
     if bool(getattr(ct, 'cone', False)):
         raise ValueError('iterative reconstruction is fan and stacked-fan only: a cone-beam scanner has no matched pair here')
     if FOV is not None and 0.5 * np.sqrt(2.0) * float(FOV) >= ct.SID:
@@ -53,14 +49,28 @@ def check_options(method, ct, n_iters, n_subsets, relax, init='fbp', FOV=None):
         raise ValueError(f"init must be 'fbp' or 'zero', not {init!r}")
     if int(n_iters) < 1:
         raise ValueError(f'n_iters = {n_iters}: at least one iteration')
+
+
+def _check_subsets(n_subsets, ct):
+    """``n_subsets`` is named in the message as the caller passes it here.  Returns the count."""
+    if not 1 <= int(n_subsets) <= ct.N_proj:
+        raise ValueError(f'n_subsets = {n_subsets} lies outside 1 .. N_proj = {ct.N_proj}')
+    return int(n_subsets)
+
+
+def check_options(method, ct, n_iters, n_subsets, relax, init='fbp', FOV=None):
+    """The argument checks of ``get_recon(..., method=)``, before any device access.  Returns the subset count."""
+    if method not in METHODS:
+        raise ValueError(f'unknown reconstruction method {method!r}; choose from {METHODS}')
+    if method == 'fbp':
+        return 1
+    _check_iteration(ct, FOV, init, n_iters)
     if not 0.0 < float(relax) < 2.0:
         raise ValueError(f'relax = {relax} lies outside (0, 2)')
     n_subsets = int(n_subsets)
     if method == 'os-sart' and n_subsets == 1:
         n_subsets = min(OS_SART_SUBSETS, ct.N_proj)
-    if not 1 <= n_subsets <= ct.N_proj:
-        raise ValueError(f'n_subsets = {n_subsets} lies outside 1 .. N_proj = {ct.N_proj}')
-    return n_subsets
+    return _check_subsets(n_subsets, ct)
 
 
 class ImageProjector:
@@ -263,17 +273,8 @@ def check_pwls_options(ct, K, n_iters, n_subsets, beta, delta, init='fbp', FOV=N
     (n_subsets, beta per channel, delta per channel)."""
     if not 1 <= int(K) <= PWLS_MAX_CHANNELS:
         raise ValueError(f'{K} channels: the joint reconstruction takes 1 .. {PWLS_MAX_CHANNELS}')
-    if bool(getattr(ct, 'cone', False)):
-        raise ValueError('iterative reconstruction is fan and stacked-fan only: a cone-beam scanner has no matched pair here')
-    if FOV is not None and 0.5 * np.sqrt(2.0) * float(FOV) >= ct.SID:
-        raise ValueError(f'FOV = {FOV} cm: the image grid does not lie strictly inside the source circle (SID = {ct.SID} cm)')
-    if init not in ('fbp', 'zero'):
-        raise ValueError(f"init must be 'fbp' or 'zero', not {init!r}")
-    if int(n_iters) < 1:
-        raise ValueError(f'n_iters = {n_iters}: at least one iteration')
-    if not 1 <= int(n_subsets) <= ct.N_proj:
-        raise ValueError(f'n_subsets = {n_subsets} lies outside 1 .. N_proj = {ct.N_proj}')
-    return int(n_subsets), per_channel(beta, K, 'beta'), per_channel(delta, K, 'delta', positive=True)
+    _check_iteration(ct, FOV, init, n_iters)
+    return _check_subsets(n_subsets, ct), per_channel(beta, K, 'beta'), per_channel(delta, K, 'delta', positive=True)
 
 
 def channels_of(n_planes):
@@ -282,6 +283,11 @@ def channels_of(n_planes):
         if K * (K + 1) // 2 == int(n_planes):
             return K
     raise ValueError(f'{n_planes} planes are no packed triangle of 1 .. {PWLS_MAX_CHANNELS} channels (1, 3 or 6 wanted)')
+
+
+def check_w_fill(w_fill):
+    if not (float(w_fill) >= 0.0 and np.isfinite(float(w_fill))):
+        raise ValueError(f'w_fill = {w_fill}: a finite value >= 0 wanted')
 
 
 def precision_weights(cov_d, w_fill=0.0):
@@ -293,8 +299,7 @@ def precision_weights(cov_d, w_fill=0.0):
         raise ValueError('cov_d must be a float64 device tensor')
     T = cov_d.shape[-1]
     K = channels_of(T)
-    if not (float(w_fill) >= 0.0 and np.isfinite(float(w_fill))):
-        raise ValueError(f'w_fill = {w_fill}: a finite value >= 0 wanted')
+    check_w_fill(w_fill)
     c = cov_d.contiguous()
     w = torch.empty((T,) + tuple(c.shape[:-1]), dtype=torch.float32, device=c.device)
     _native.check(_native.load().dexct_cov_precision(ptr(c), c.numel() // T, K, float(w_fill), ptr(w), stream_ptr()),
