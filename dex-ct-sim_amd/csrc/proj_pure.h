@@ -1,5 +1,6 @@
 // Decisions of the projection host layer that are pure functions of integers: no HIP, no environment, nothing but <stdint.h>, so
-// that a stand-alone host program can run them (tests/air_map_host.cpp, also under the sanitizers).  proj_host.h includes this.
+// that a stand-alone host program can run them (tests/air_map_host.cpp, tests/uniform_count_host.cpp, also under the sanitizers).
+// proj_host.h includes this.
 #pragma once
 #include <stdint.h>
 
@@ -20,6 +21,32 @@ inline bool use_air_map(int mode, bool have_map, int64_t n_air_columns, int64_t 
   const int64_t first = (n_cols / kAirMapShareDen) * kAirMapShareNum +
                         ((n_cols % kAirMapShareDen) * kAirMapShareNum + kAirMapShareDen - 1) / kAirMapShareDen;
   return n_air_columns >= first;
+}
+
+// ---- the column-class map (dexct_siddon_project_packed_uniform): the counts the builder gave, and whether a launch looks
+// columns up in the map.  n_uniform[id], id = 0 .. 3: columns that hold id over all z.
+// The counts a builder can have given: none negative, together no more than the grid has columns (summed without overflow).
+inline bool class_counts_ok(const int64_t* n_uniform, int64_t n_cols) {
+  if (!n_uniform || n_cols <= 0) return false;
+  int64_t sum = 0;
+  for (int id = 0; id < 4; ++id) {
+    if (n_uniform[id] < 0 || n_uniform[id] > n_cols - sum) return false;
+    sum += n_uniform[id];
+  }
+  return true;
+}
+// mode: DEXCT_P16_UNIFORM (knob::kP16Uniform) - 0 never (the air map serves alone, under its own rule), 1 when it pays, 2 whenever
+// there is a class map; air_mode: DEXCT_P16_AIR_SKIP, whose 0 turns every map off.  A lookup in the class map costs what one in
+// the air map costs and a dropped slab gives back the same sweeps, so mode 1 carries the share of the air map over: the class map
+// is used from kAirMapShareNum / kAirMapShareDen DROPPABLE columns on - columns uniform in any id (profiles/rows16_uniform.md
+// has the measurement on a volume where nothing but air is droppable).  Impossible counts never use the map.
+inline bool use_class_map(int mode, int air_mode, bool have_map, const int64_t* n_uniform, int64_t n_cols) {
+  if (!have_map || mode == 0 || air_mode == 0 || !class_counts_ok(n_uniform, n_cols)) return false;
+  if (mode == 2) return true;
+  const int64_t droppable = n_uniform[0] + n_uniform[1] + n_uniform[2] + n_uniform[3];      // <= n_cols: class_counts_ok
+  const int64_t first = (n_cols / kAirMapShareDen) * kAirMapShareNum +
+                        ((n_cols % kAirMapShareDen) * kAirMapShareNum + kAirMapShareDen - 1) / kAirMapShareDen;
+  return droppable >= first;
 }
 
 }  // namespace proj

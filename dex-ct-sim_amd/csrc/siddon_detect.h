@@ -63,7 +63,12 @@ struct PackedArgs {
   // quantum noise (the NOISY instantiations; ABI 6): the kernel detects the variance with the counts and, `sample` != 0, draws
   // the sample itself (noise_sample.h; the Philox counter needs the GLOBAL view)
   int view_begin;
-  int sample;
+  // (the noise-free SKIP forms draw nothing and read the word as col_class instead: != 0 = col_air points to a column-CLASS map,
+  // dexct_volume_column_classes.  One word for both so that the struct, and with it every other form of the kernel, stays as it was)
+  union {
+    int sample;
+    int col_class;
+  };
   uint32_t seed_lo, seed_hi;
   // air-column map (dexct_volume_air_columns): bit y * nx + x set = column (x, y) of vol_z2 is 0 over all z; the classification
   // enters no slab whose pieces inside the grid all lie in such columns.  Null: every slab is entered.

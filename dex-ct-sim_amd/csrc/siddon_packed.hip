@@ -26,11 +26,22 @@
 // from another such column.  dexct_volume_air_columns marks these columns in a bit map (once per volume) and the SKIP forms of
 // the kernel (dexct_siddon_project_packed_skip) enter no slab in their lists whose pieces all lie in marked columns: the sweeps
 // get shorter, every sum keeps its bits (profiles/rows16_air_skip.md).
+//
+// Uniform columns.  A column that holds ONE id over all z - the water of an extruded cylinder, not only the air round it - adds
+// the same word to every lane, so every slab in such columns adds the same integer to all the counters of a pair.
+// dexct_volume_column_classes classes every column as mixed or uniform in an id (four bits per column, once per volume) and the
+// noise-free SKIP forms (dexct_siddon_project_packed_uniform) also leave out the full slabs in uniform columns and the crossing
+// slabs between two columns of the same id; each lane counts what it left out per id in one register, one sum over the pair's
+// lanes follows the slab loop, and the pair's integers join every row's integer before it becomes a float.  The lists, their
+// order, the sweeps, correct() and everything behind the un-slicing are what they were (uniform_count.h has the rule and the
+// argument; profiles/rows16_uniform.md the measurements).  The same forms read an air map as a class map of air and mixed
+// columns; the noisy SKIP forms keep the air rule.
 #include "common.h"
 #include "dedup_index.h"
 #include "noise_sample.h"
 #include "proj_host.h"
 #include "sliced_count.h"
+#include "uniform_count.h"
 
 namespace dexct {
 
@@ -46,6 +57,12 @@ static_assert(kP16Super % kFullTrip == 0 && kP16Super % kCrossTrip == 0, "the li
 __host__ __device__ constexpr int p16_lds_bytes(int n_pairs) {
   const int lists = n_pairs * kP16Super * (int)(sizeof(CrossRec) + sizeof(uint32_t));
   return lists < 2 * 64 * 64 ? 2 * 64 * 64 : lists;
+}
+// Which SKIP forms take a column-class map (kernel and host agree through this): the noise-free ones, but for the unstaged
+// three-material form.  That form sits at the 128 VGPRs of its four waves per SIMD and spilled 3 of them to scratch with the
+// count in it; the noisy forms have no register to spare either (three materials: 127).  The forms left out keep the air rule.
+__host__ __device__ constexpr bool p16_by_class(int n_materials, bool staged, bool noisy) {
+  return !noisy && !(n_materials == 3 && !staged);
 }
 // what the list of distinct quads (dedup_index.h) keeps behind itself, in the last bytes of the wave's LDS - not in registers:
 // the detection rounds have none to spare
@@ -141,6 +158,10 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
   const unsigned long long group_mask = (lpp == 64 ? ~0ull : ((1ull << lpp) - 1ull)) << (g * lpp);
   const unsigned long long below_mask = group_mask & ((1ull << lane) - 1ull);
   static_assert(!(GROUPED && SKIP), "the group passes take no map");
+  // the noise-free SKIP forms class columns as mixed or uniform in an id (a class map; an air map read as one) and count the
+  // slabs they leave out, per id.  The other SKIP forms keep the air rule and the code they had (p16_by_class).
+  constexpr bool kByClass = SKIP && p16_by_class(NM, STAGED, NOISY);
+  uint32_t dropped = 0u;                     // this lane's dropped slabs (ucount::bump), over all passes
   for (int s0 = 0; s0 < n_slabs_max; s0 += kP16Super) {
     // ---- geometry: the lanes of a pair classify its slabs s0 + li, s0 + li + lpp, ... (slab order kept per pair)
     int run_f = 0, run_c = 0;               // per pair (identical in all lanes of a pair)
@@ -149,9 +170,13 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
     // words are 0: they add nothing to a counter and two equal words cause no correction, so every sum keeps its bits; the
     // slabs that stay keep their order.  A crossing slab with one air piece stays (its count and its correction are needed).
     // The offsets are column index x zb: the same integers as i * su + j * sv.
+    // kByClass (the noise-free SKIP forms): the map is of either kind (uniform_count.h: one lookup for both) and a slab also
+    // leaves when both its pieces lie in columns uniform in the same id; the lane counts it in `dropped` (one field per id).
+    // The argument why every output keeps its bytes stands in uniform_count.h.
     for (int q0 = 0; SKIP && q0 < kP16Super; q0 += kAirBatch * lpp) {
       const uint32_t cu = axis == 0 ? 1u : (uint32_t)a.g.nx, cv = axis == 0 ? (uint32_t)a.g.nx : 1u;
-      const uint32_t last_word = ((uint32_t)a.g.nx * (uint32_t)a.g.ny - 1u) >> 5;
+      const ucount::MapKind mk = ucount::map_kind(kByClass && pa.col_class != 0);       // (wave-uniform)
+      const uint32_t last_word = ((uint32_t)a.g.nx * (uint32_t)a.g.ny - 1u) >> (kByClass ? mk.word_shift : 5u);
       uint32_t cola[kAirBatch], colb[kAirBatch], wa[kAirBatch], wb[kAirBatch];
       float tt[kAirBatch];
       bool ina[kAirBatch], inb[kAirBatch], one[kAirBatch];          // one: both pieces in the same column
@@ -173,13 +198,27 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
         }
         // (a piece outside the grid, and a lane without a slab, look at word 0 and ignore it; the map is read through a plain
         // pointer, not a bounds-checked buffer, so the word index is held inside it whatever the plan says)
-        wa[u] = pa.col_air[ina[u] ? min(cola[u] >> 5, last_word) : 0u];
-        wb[u] = pa.col_air[inb[u] ? min(colb[u] >> 5, last_word) : 0u];
+        if constexpr (kByClass) {
+          wa[u] = pa.col_air[ina[u] ? min(ucount::word_of(cola[u], mk), last_word) : 0u];
+          wb[u] = pa.col_air[inb[u] ? min(ucount::word_of(colb[u], mk), last_word) : 0u];
+        } else {
+          wa[u] = pa.col_air[ina[u] ? min(cola[u] >> 5, last_word) : 0u];
+          wb[u] = pa.col_air[inb[u] ? min(colb[u] >> 5, last_word) : 0u];
+        }
       }
 #pragma unroll
       for (int u = 0; u < kAirBatch; ++u) {
-        const bool air_a = !ina[u] || ((wa[u] >> (cola[u] & 31u)) & 1u), air_b = !inb[u] || ((wb[u] >> (colb[u] & 31u)) & 1u);
-        const bool keep = !(air_a && air_b);
+        bool keep;
+        if constexpr (kByClass) {
+          // (a lane without a slab has no piece inside: air on both sides, dropped, and air counts nothing)
+          const uint32_t ea = ina[u] ? ucount::class_in(wa[u], cola[u], mk) : ucount::kAirClass;
+          const uint32_t eb = inb[u] ? ucount::class_in(wb[u], colb[u], mk) : ucount::kAirClass;
+          keep = !ucount::droppable(ea, eb);
+          dropped += keep ? 0u : ucount::bump(eb);
+        } else {
+          const bool air_a = !ina[u] || ((wa[u] >> (cola[u] & 31u)) & 1u), air_b = !inb[u] || ((wb[u] >> (colb[u] & 31u)) & 1u);
+          keep = !(air_a && air_b);
+        }
         const bool whole = ina[u] && inb[u] && one[u];
         const bool is_full = whole && keep, is_cross = !whole && (ina[u] || inb[u]) && keep;
         const uint32_t offa = ina[u] ? cola[u] * zb : kOob, offb = inb[u] ? colb[u] * zb : kOob;
@@ -269,6 +308,22 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
     }
     __builtin_amdgcn_wave_barrier();
   }
+  // kByClass: ONE sum over the lanes of each pair (all 64 lanes are here; a pair is an aligned power of two of them) gives the
+  // pair's dropped slabs per id, and from them what the sweeps would have added to every row's counter of each flag plane:
+  // id 1 sets plane 0, id 2 plane 1, id 3 both and the "both" plane.
+  uint32_t drop0 = 0u, drop1 = 0u, drop3 = 0u;
+  if constexpr (kByClass) {
+    uint32_t lo = ucount::spread_lo(dropped), mid = ucount::spread_mid(dropped);
+    for (int d = 1; d < lpp; d <<= 1) {
+      lo += (uint32_t)__shfl_xor((int)lo, d);
+      mid += (uint32_t)__shfl_xor((int)mid, d);
+    }
+    drop3 = lo >> 16;
+    drop0 = (lo & 0xFFFFu) + drop3;
+    drop1 = mid + drop3;
+    // (the un-slicing below holds up to 64 words: it must not be drawn up between the shuffles to hide their latency)
+    __builtin_amdgcn_sched_barrier(0);
+  }
   // STAGED (the usual case: row-fastest output, whole groups of 4 rows, one or two spectra): each detection round leaves
   // its results in LDS and the wave stores them at the end, so that one store instruction writes 1 KiB of consecutive
   // addresses (whole lines) instead of 64 separate 16-byte pieces per round - every lane's 64 output bytes used to
@@ -293,6 +348,11 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
     if (BOTH) cnt3.unslice(n3);
 #pragma unroll
     for (int row = 0; row < 16; ++row) {
+      if constexpr (kByClass) {                // the dropped slabs join the integers they were left out of, before the conversion
+        n[2 * row] += drop0;
+        n[2 * row + 1] += drop1;
+        if (BOTH) n3[2 * row] += drop3;
+      }
       if (BOTH) {
         corr[0][row] = (float)(int32_t)(n[2 * row] - n3[2 * row]) + corr[0][row];
         corr[1][row] = (float)(int32_t)(n[2 * row + 1] - n3[2 * row]) + corr[1][row];
@@ -648,7 +708,49 @@ __global__ __launch_bounds__(256) void col_air_kernel(const uint8_t* __restrict_
   }
 }
 
-// the grid cap of col_air_kernel (one column per thread)
+// The column-class map of the packed volume (uniform_count.h, include/dexct_p16_uniform.h): nibble c % 8 of word c / 8 is
+// ucount::class_of(id) iff all zb bytes of column c = y * nx + x hold id in each of their four voxels, else 0 (mixed); the nibbles
+// past the last column stay 0.  Chunks of 256 columns per workgroup as in col_air_kernel; the three bit planes of a wave's 64
+// classes come from three ballots and its first eight lanes write a word each.  n_uniform[id] receives the uniform columns per id.
+__global__ __launch_bounds__(256) void col_class_kernel(const uint8_t* __restrict__ vol_z2, uint32_t n_cols, uint32_t zb,
+                                                        uint32_t* __restrict__ col_class, unsigned long long* __restrict__ n_uniform) {
+  const uint32_t n_chunks = (n_cols + 255u) / 256u, n_words = (n_cols + 7u) / 8u;
+  const bool dwords = (zb & 3u) == 0 && (reinterpret_cast<uintptr_t>(vol_z2) & 3u) == 0;
+  for (uint32_t ch = blockIdx.x; ch < n_chunks; ch += gridDim.x) {
+    const uint32_t col = ch * 256u + threadIdx.x;
+    uint32_t cls = 0u;
+    if (col < n_cols) {
+      const uint8_t* q = vol_z2 + (size_t)col * zb;
+      const uint32_t id = q[0] & 3u;
+      uint32_t diff = 0u;
+      if (dwords)
+        for (uint32_t k = 0; k < zb; k += 4) diff |= *reinterpret_cast<const uint32_t*>(q + k) ^ (id * 0x55555555u);
+      else
+        for (uint32_t k = 0; k < zb; ++k) diff |= (uint32_t)q[k] ^ (id * 0x55u);
+      cls = diff == 0u ? ucount::class_of(id) : 0u;
+    }
+    const unsigned long long m0 = __ballot(cls & 1u), m1 = __ballot(cls & 2u), m2 = __ballot(cls & 4u);
+    const uint32_t sub = threadIdx.x & 63u;
+    if (sub < 8u) {
+      const uint32_t wi = ((ch * 256u + threadIdx.x - sub) >> 3) + sub;
+      uint32_t word = 0u;
+#pragma unroll
+      for (uint32_t j = 0; j < 8u; ++j) {
+        const uint32_t at = 8u * sub + j;
+        word |= ((uint32_t)((m0 >> at) & 1u) | (uint32_t)((m1 >> at) & 1u) << 1 | (uint32_t)((m2 >> at) & 1u) << 2) << (4u * j);
+      }
+      if (wi < n_words) col_class[wi] = word;
+    }
+    if (sub == 0u && m0) {
+      const unsigned long long per_id[4] = {m0 & ~m1 & ~m2, m0 & m1 & ~m2, m0 & ~m1 & m2, m0 & m1 & m2};
+#pragma unroll
+      for (int id = 0; id < 4; ++id)
+        if (per_id[id]) atomicAdd(n_uniform + id, (unsigned long long)__popcll(per_id[id]));
+    }
+  }
+}
+
+// the grid cap of col_air_kernel and col_class_kernel (one column per thread)
 constexpr int kColAirMaxBlocks = 4096;
 
 // Material groups on the packed volume: ids 3g+1..3g+3 -> codes 1..3, everything else 0 (group_codes_kernel of
@@ -768,6 +870,21 @@ int dexct_volume_air_columns(const uint8_t* vol_z2, int32_t nx, int32_t ny, int3
   return DEXCT_OK;
 }
 
+int dexct_volume_column_classes(const uint8_t* vol_z2, int32_t nx, int32_t ny, int32_t nz, uint32_t* col_class, uint64_t* n_uniform,
+                                void* stream) {
+  if (!vol_z2 || !col_class || !n_uniform || nx < 1 || ny < 1 || nz < 4 || (nz & 3)) return DEXCT_EINVAL;
+  if ((uint64_t)nx * ny > 0x7FFFFF00ull) return DEXCT_ERANGE;                 // 32-bit column indices (whole chunks of 256)
+  const uint32_t n_cols = (uint32_t)nx * (uint32_t)ny;
+  hipStream_t st = as_stream(stream);
+  DEXCT_HIP_TRY(hipMemsetAsync(n_uniform, 0, 4 * sizeof(uint64_t), st));
+  uint32_t nblk = (n_cols + 255u) / 256u;
+  if (nblk > (uint32_t)kColAirMaxBlocks) nblk = kColAirMaxBlocks;
+  hipLaunchKernelGGL(col_class_kernel, dim3(nblk), dim3(256), 0, st, vol_z2, n_cols, (uint32_t)nz >> 2, col_class,
+                     reinterpret_cast<unsigned long long*>(n_uniform));
+  DEXCT_LAUNCH_CHECK();
+  return DEXCT_OK;
+}
+
 int dexct_siddon_project_packed(const dexct_fan_geom* geom, const dexct_ray_plan* plan, int32_t view_begin,
                                 int32_t view_end, const uint8_t* vol_z2, int32_t n_materials, int32_t n_energies,
                                 int32_t n_spectra, const float* mu, const float* weights, float* counts, float* pathlen,
@@ -782,6 +899,17 @@ int dexct_siddon_project_packed_skip(const dexct_fan_geom* geom, const dexct_ray
                                      int32_t n_spectra, const float* mu, const float* weights, float* counts, float* pathlen,
                                      int32_t layout, const dexct_log_out* log_out, const float* weights2, float* variance,
                                      const dexct_noise* noise, const uint32_t* col_air, int64_t n_air_columns, void* stream) {
+  return dexct_siddon_project_packed_uniform(geom, plan, view_begin, view_end, vol_z2, n_materials, n_energies, n_spectra, mu,
+                                             weights, counts, pathlen, layout, log_out, weights2, variance, noise, col_air,
+                                             n_air_columns, nullptr, nullptr, stream);
+}
+
+int dexct_siddon_project_packed_uniform(const dexct_fan_geom* geom, const dexct_ray_plan* plan, int32_t view_begin,
+                                        int32_t view_end, const uint8_t* vol_z2, int32_t n_materials, int32_t n_energies,
+                                        int32_t n_spectra, const float* mu, const float* weights, float* counts, float* pathlen,
+                                        int32_t layout, const dexct_log_out* log_out, const float* weights2, float* variance,
+                                        const dexct_noise* noise, const uint32_t* col_air, int64_t n_air_columns,
+                                        const uint32_t* col_class, const int64_t* n_uniform_columns, void* stream) {
   if (!geom || !plan || !vol_z2 || !mu || !weights || !counts) return DEXCT_EINVAL;
   if (n_energies < 1 || n_spectra < 1) return DEXCT_EINVAL;
   if (n_materials < 2 || n_materials > 4 || n_spectra > DEXCT_MAX_SPECTRA) return DEXCT_ERANGE;     // ids 0..3
@@ -797,13 +925,11 @@ int dexct_siddon_project_packed_skip(const dexct_fan_geom* geom, const dexct_ray
   l.pa.vol_z2 = vol_z2;
   const int64_t n_cols = (int64_t)geom->nx * geom->ny;
   if (col_air && (n_air_columns < 0 || n_air_columns > n_cols)) return DEXCT_EINVAL;
-  // the map costs a few instructions per slab and lane and pays them back with the slabs it drops: proj::use_air_map
-  l.pa.col_air = proj::use_air_map(proj::read_knob(proj::knob::kP16AirSkip), col_air != nullptr, n_air_columns, n_cols) ? col_air : nullptr;
-  proj::copy_noise(l.pa, view_begin, nl);     // (rows16_kernel draws the sample itself: PackedArgs, not its ProjArgs)
+  if (col_class && (!n_uniform_columns || !proj::class_counts_ok(n_uniform_columns, n_cols))) return DEXCT_EINVAL;
+  const bool noisy = weights2 != nullptr;
   l.t = Tables{mu, weights, weights2};
   l.st = as_stream(stream);
   l.staged_store = proj::read_knob(proj::knob::kP16Staged) != 0;
-  const bool noisy = weights2 != nullptr;
   // whole-line stores through LDS (STAGED) wherever the output allows them: row-fastest layout, whole groups of 4 rows,
   // one or two spectra (what the stage holds)
   const bool staged = l.staged_store && layout == 1 && geom->n_rows % 4 == 0 && n_spectra <= 2;
@@ -814,8 +940,18 @@ int dexct_siddon_project_packed_skip(const dexct_fan_geom* geom, const dexct_ray
   // without; every other value is 4 - and any value but 4 and 5 has always cost the staged store
   const int minw = (noisy || n_materials != 3) ? 4 : proj::read_knob(proj::knob::kP16MinW);
   const bool minw_form = minw == 5 || minw == 6 || minw == 8;
-  // with the air-column map: the SKIP forms, which exist for the default MINW only
-  if (l.pa.col_air && !minw_form) return launch_p16_skip(l, n_materials, staged && minw == 4, noisy);
+  const bool skip_staged = staged && minw == 4;            // the SKIP form a map would run
+  // a map costs a few instructions per slab and lane and pays them back with the slabs it drops: proj::use_class_map for the
+  // class map (the SKIP forms that take one: p16_by_class), else proj::use_air_map for the air map
+  const int air_mode = proj::read_knob(proj::knob::kP16AirSkip);
+  const bool by_class = p16_by_class(n_materials, skip_staged, noisy) &&
+                        proj::use_class_map(proj::read_knob(proj::knob::kP16Uniform), air_mode, col_class != nullptr, n_uniform_columns, n_cols);
+  if (by_class) l.pa.col_air = col_class;
+  else l.pa.col_air = proj::use_air_map(air_mode, col_air != nullptr, n_air_columns, n_cols) ? col_air : nullptr;
+  proj::copy_noise(l.pa, view_begin, nl);     // (rows16_kernel draws the sample itself: PackedArgs, not its ProjArgs)
+  if (!noisy) l.pa.col_class = by_class ? 1 : 0;      // (the word is `sample` to the noisy forms)
+  // with a map: the SKIP forms, which exist for the default MINW only
+  if (l.pa.col_air && !minw_form) return launch_p16_skip(l, n_materials, skip_staged, noisy);
   if (noisy) {
     if (n_materials == 2) return staged ? launch_p16<2, 4, false, true, true>(l) : launch_p16<2, 4, false, false, true>(l);
     if (n_materials == 4) return staged ? launch_p16<4, 3, false, true, true>(l) : launch_p16<4, 3, false, false, true>(l);

@@ -833,5 +833,6 @@ int dexct_pwls_update(const float* x_old, const float* g, const float* d, int32_
 #endif
 
 #include "dexct_gn_dedup.h"      /* additive to ABI 6: the Newton decomposition that solves repeated rows once */
+#include "dexct_p16_uniform.h"   /* additive to ABI 6: the column-class map and the packed projection that uses it */
 
 #endif /* DEXCT_H */
