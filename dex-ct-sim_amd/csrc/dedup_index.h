@@ -66,6 +66,35 @@ DEXCT_DEDUP_HD bool use_list(int n_fresh, int live_rounds, int n_materials, int 
   return (long long)n_fresh * entry_bytes(n_materials) + reserve_bytes <= (long long)lds_bytes;
 }
 
+// ---- Narrow rounds.  A round of 64 entries detects four rows per lane: lane j takes entry 64 k + j.  The LAST round of a list
+// may hold far fewer entries than the wave has lanes (an extruded wave: one entry per pair), and what a round costs follows the
+// rows a lane carries, not the lanes that work.  So a last round of at most 32 entries runs with TWO rows per lane (lane j: rows
+// 2 (j & 1), + 1 of entry 64 k + (j >> 1)) and one of at most 16 with ONE (lane j: row j & 3 of entry 64 k + (j >> 2)).
+// The rows of a round are wave-uniform: a function of n_fresh and k alone.
+constexpr int kRowsPerQuad = 4;
+
+// entries of round k (0: the list has no such round)
+DEXCT_DEDUP_HD int round_entries(int n_fresh, int k) {
+  const int left = n_fresh - kWaveLanes * k;
+  return left < 0 ? 0 : (left > kWaveLanes ? kWaveLanes : left);
+}
+// rows per lane of round k: 1, 2 or 4.  min_rows: the narrowest form the caller has (a kernel built without the one-row form
+// runs its shortest lists two rows per lane)
+DEXCT_DEDUP_HD int round_rows(int n_fresh, int k, int min_rows = 1) {
+  const int n = round_entries(n_fresh, k);
+  const int rows = n <= kWaveLanes / 4 ? 1 : (n <= kWaveLanes / 2 ? 2 : kRowsPerQuad);
+  return rows < min_rows ? min_rows : rows;
+}
+// the entry lane j detects in round k at `rows` rows per lane, and the first of its rows inside the entry
+DEXCT_DEDUP_HD int lane_entry(int rows, int k, int lane) { return kWaveLanes * k + lane / (kRowsPerQuad / rows); }
+DEXCT_DEDUP_HD int lane_first_row(int rows, int lane) { return (lane % (kRowsPerQuad / rows)) * rows; }
+// whether the lane has an entry at all (the others detect air and store nothing)
+DEXCT_DEDUP_HD bool lane_live(int n_fresh, int rows, int k, int lane) { return lane_entry(rows, k, lane) < n_fresh; }
+// Byte offsets inside an entry of the piece (4 * rows bytes) a lane reads for the m-th material that has a sum (m = 0: material 1)
+// and of the piece it writes for spectrum slot s: the results go over the sums, as with four rows
+DEXCT_DEDUP_HD int piece_in(int m, int first_row) { return 16 * m + 4 * first_row; }
+DEXCT_DEDUP_HD int piece_out(int s, int first_row) { return 16 * s + 4 * first_row; }
+
 // the pair (channel of the wave) a list entry belongs to: pair_end[k] = fresh quads of the pairs 0..k (ascending; the entries
 // of a pair are consecutive)
 DEXCT_DEDUP_HD int entry_pair(int entry, const int (&pair_end)[4], int n_pairs) {

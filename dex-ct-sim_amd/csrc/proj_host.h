@@ -154,7 +154,8 @@ constexpr Knob kRaysBatch{"DEXCT_RAYS_BATCH", 4, INT_MIN, INT_MAX};
 constexpr Knob kDetMasks{"DEXCT_DET_MASKS", 1, INT_MIN, INT_MAX};
 // rows16_kernel, 3 and 4 materials: a wave whose rays all miss the last material runs the detection of one material less; 0 = off
 constexpr Knob kDetAbsent{"DEXCT_DET_ABSENT", 1, INT_MIN, INT_MAX};
-// rows16_kernel, staged noise-free forms: a wave detects each distinct quad of rows once where that saves a round; 0 = off
+// rows16_kernel, staged noise-free forms: a wave detects each distinct quad of rows once where that saves a round; 0 = off,
+// 2 = every list round detects four rows per lane (no narrow last round: the A/B of dedup_index.h's round_rows)
 constexpr Knob kDetDedup{"DEXCT_DET_DEDUP", 1, INT_MIN, INT_MAX};
 // rows16_kernel: store the results of a wave through LDS as whole lines; 0 = per-round 16-B stores
 constexpr Knob kP16Staged{"DEXCT_P16_STAGED", 1, INT_MIN, INT_MAX};

@@ -58,7 +58,7 @@ struct PackedArgs {
   int det_masks;           // skip detection FMAs of spectrum slots with zero weights (blocks of four energies)
   int det_absent;          // detect waves whose rays all miss the last material without it (DEXCT_DET_ABSENT=0: off)
   // the staged noise-free forms detect each distinct quad of rows once per wave (siddon_packed.hip, dedup_index.h;
-  // DEXCT_DET_DEDUP=0: every quad is detected).  (The word held DEXCT_P16_STAGED, which only the host reads: P16Launch::staged_store.)
+  // DEXCT_DET_DEDUP=0: every quad is detected; 2: the list without its narrow last round).  (The word held DEXCT_P16_STAGED, which only the host reads: P16Launch::staged_store.)
   int det_dedup;
   // quantum noise (the NOISY instantiations; ABI 6): the kernel detects the variance with the counts and, `sample` != 0, draws
   // the sample itself (noise_sample.h; the Philox counter needs the GLOBAL view)
@@ -321,8 +321,8 @@ struct AirCache {
 // FVAR (with res_out and var_out, at most two spectra): the variances sum_e w2[s][e] exp(-...) come out of the same energy
 // loop as the counts (detect_energies<.., VAR>) and are handed to the caller like the counts - the kernels that draw the
 // noise sample themselves.  Same bits as the separate loop below.
-// SHORT (R = 4, NM >= 3, at most two spectra; bm.drop_last): a wave none of whose rays crosses the LAST material runs the energy
-// loop of NM - 1 materials.  The last exponent FMA of such a ray is fma(mu, 0, pe) = pe for finite mu (pe is never -0: its
+// SHORT (NM >= 3, at most two spectra; bm.drop_last; any R - the narrow list rounds of rows16_kernel detect two rows per lane):
+// a wave none of whose rays crosses the LAST material runs the energy loop of NM - 1 materials.  The last exponent FMA of such a ray is fma(mu, 0, pe) = pe for finite mu (pe is never -0: its
 // chain starts from +0), so every exponent, and with it every sum, keeps its bits; one v_pk_fma_f32 per pair and energy less.
 template <int NM, int R, bool EXTRAS = true, bool FVAR = false, bool SHORT = false>
 __device__ __forceinline__ void detect_store(const float (&L)[R][NM], const ProjArgs& a, const float* __restrict__ mu,
@@ -383,7 +383,7 @@ __device__ __forceinline__ void detect_store(const float (&L)[R][NM], const Proj
     }
   }
   bool wave_short = false;
-  if constexpr (SHORT && R == 4 && NM >= 3) {
+  if constexpr (SHORT && NM >= 3) {
     if (a.n_spectra <= 2 && bm.drop_last && !wave_air) {
       bool lane_none = true;
 #pragma unroll
@@ -418,7 +418,7 @@ __device__ __forceinline__ void detect_store(const float (&L)[R][NM], const Proj
       if constexpr (FVAR) { accv[0][q] = onev[0][0]; accv[1][q] = onev[1][0]; }
     }
   } else if (wave_short) {
-    if constexpr (SHORT && R == 4 && NM >= 3) {
+    if constexpr (SHORT && NM >= 3) {
       f32x2 Ls[(R + 1) / 2][NM - 1];
 #pragma unroll
       for (int j = 0; j < (R + 1) / 2; ++j)

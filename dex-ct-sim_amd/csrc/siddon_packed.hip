@@ -173,7 +173,67 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
     // kByClass (the noise-free SKIP forms): the map is of either kind (uniform_count.h: one lookup for both) and a slab also
     // leaves when both its pieces lie in columns uniform in the same id; the lane counts it in `dropped` (one field per id).
     // The argument why every output keeps its bytes stands in uniform_count.h.
-    for (int q0 = 0; SKIP && q0 < kP16Super; q0 += kAirBatch * lpp) {
+    // kLeanClass (the staged noise-free SKIP forms; the others keep the loop below as it was - the unstaged three-material form
+    // spilled 2 VGPRs to scratch with the first two changes): the same classification, the same lists, with less work per slab.
+    //   - The trips end with the slots that can hold a slab of the wave's longest ray (whole batches; wave-uniform): the last
+    //     pass of a 446-slab ray has 62 live slots of 128, and the padding and the sweeps below cope with short lists anyway.
+    //   - The slab coordinate V0 + (i_first + s) SV is formed once per pass and lane, for the lane's first slab, and moves on by
+    //     lpp SV per iteration: the same integer modulo 2^64 as the product per slab.
+    //   - The slab geometry runs without a branch (a lane without a slab has no piece inside: `have`), and the column index
+    //     i cu + j cv is formed with 24-bit multiplies (i < 2^13, j < nv <= 2047 for a piece inside, cu, cv <= 2047; the index
+    //     of a piece outside is not used).
+    //   - The map is read through a bounds-checked buffer of exactly its words: an index beyond it - a piece outside the grid,
+    //     whose word is ignored anyway - returns 0 without an access, so no index is clamped or replaced.  A piece outside the
+    //     grid classes as air through ina / inb as before, never through the word.
+    //   - The offsets col x zb are formed only where a slab is written to a list.
+    constexpr bool kLeanClass = SKIP && STAGED && !NOISY;
+    if constexpr (kLeanClass) {
+      const uint32_t cu = axis == 0 ? 1u : (uint32_t)a.g.nx, cv = axis == 0 ? (uint32_t)a.g.nx : 1u;
+      const ucount::MapKind mk = ucount::map_kind(pa.col_class != 0);       // (wave-uniform)
+      const __amdgpu_buffer_rsrc_t map_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<uint32_t*>(pa.col_air), 0, (int)(4u * ucount::map_words((uint32_t)a.g.nx * (uint32_t)a.g.ny, mk)), 0x00020000);
+      const int q_end = min(kP16Super, (n_slabs_max - s0 + kAirBatch * lpp - 1) & ~(kAirBatch * lpp - 1));
+      unsigned long long va_next = (unsigned long long)p.V0 + (unsigned long long)((long long)(p.i_first + s0 + li) * p.SV);
+      const unsigned long long va_step = (unsigned long long)p.SV * (unsigned long long)lpp;
+      for (int q0 = 0; q0 < q_end; q0 += kAirBatch * lpp) {
+        uint32_t cola[kAirBatch], colb[kAirBatch], wa[kAirBatch], wb[kAirBatch];
+        float tt[kAirBatch];
+        bool ina[kAirBatch], inb[kAirBatch], one[kAirBatch];          // one: both pieces in the same column
+#pragma unroll
+        for (int u = 0; u < kAirBatch; ++u) {
+          const int s = s0 + q0 + u * lpp + li;
+          const bool have = s < p.n_slabs;
+          const SlabPieces sp = dda_slab((long long)va_next, p.SV, smask, p.kf);
+          va_next += va_step;
+          ina[u] = have && (uint32_t)sp.ja < (uint32_t)nv;
+          inb[u] = have && (uint32_t)sp.jb < (uint32_t)nv;
+          const uint32_t icu = __umul24((uint32_t)(p.i_first + s), cu);
+          cola[u] = icu + __umul24((uint32_t)sp.ja, cv);
+          colb[u] = icu + __umul24((uint32_t)sp.jb, cv);
+          one[u] = sp.ja == sp.jb;
+          tt[u] = sp.t;
+          wa[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(map_rsrc, (int)(ucount::word_of(cola[u], mk) << 2), 0, 0);
+          wb[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(map_rsrc, (int)(ucount::word_of(colb[u], mk) << 2), 0, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < kAirBatch; ++u) {
+          // (a lane without a slab has no piece inside: air on both sides, dropped, and air counts nothing)
+          const uint32_t ea = ina[u] ? ucount::class_in(wa[u], cola[u], mk) : ucount::kAirClass;
+          const uint32_t eb = inb[u] ? ucount::class_in(wb[u], colb[u], mk) : ucount::kAirClass;
+          const bool keep = !ucount::droppable(ea, eb);
+          dropped += keep ? 0u : ucount::bump(eb);
+          const bool whole = ina[u] && inb[u] && one[u];
+          const bool is_full = whole && keep, is_cross = !whole && (ina[u] || inb[u]) && keep;
+          const unsigned long long mf = __ballot(is_full), mc = __ballot(is_cross);
+          if (is_full) list_full[g][run_f + __popcll(mf & below_mask)] = colb[u] * zb;
+          if (is_cross)
+            list_cross[g][run_c + __popcll(mc & below_mask)] = CrossRec{ina[u] ? cola[u] * zb : kOob, inb[u] ? colb[u] * zb : kOob, tt[u], 0u};
+          run_f += __popcll(mf & group_mask);
+          run_c += __popcll(mc & group_mask);
+        }
+      }
+    }
+    for (int q0 = 0; SKIP && !kLeanClass && q0 < kP16Super; q0 += kAirBatch * lpp) {
       const uint32_t cu = axis == 0 ? 1u : (uint32_t)a.g.nx, cv = axis == 0 ? (uint32_t)a.g.nx : 1u;
       const ucount::MapKind mk = ucount::map_kind(kByClass && pa.col_class != 0);       // (wave-uniform)
       const uint32_t last_word = ((uint32_t)a.g.nx * (uint32_t)a.g.ny - 1u) >> (kByClass ? mk.word_shift : 5u);
@@ -398,7 +458,10 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
   // in it it took 99, or 96 with 3 of them spilled to scratch; its SKIP form runs four waves either way and has the list.)
   constexpr bool kDedup = STAGED && !NOISY && !GROUPED && !(NM == 2 && !SKIP);
   constexpr int kEntry = dedup::entry_bytes(NM);
+  constexpr int kNarrowRows = 2;             // the narrowest list round built: lists of at most 16 entries take the two-row round too
+  constexpr bool kNarrow = kDedup && MINW == (NM == 4 ? 3 : 4);      // (the DEXCT_P16_MINW forms keep four-row rounds: A/B forms)
   int list_rounds = 0;                       // > 0: the wave detects its list, in so many rounds
+  int list_fresh = 0;                        // entries of that list (wave-uniform: popcounts of ballots)
   auto dedup_tail = [&]() { return reinterpret_cast<DedupTail*>(reinterpret_cast<uint8_t*>(lds_lists) + p16_lds_bytes(n_pairs) - sizeof(DedupTail)); };
   float chord_u = p.chord_u, len_per_u = p.len_per_u;
   if constexpr (kDedup) {
@@ -428,6 +491,7 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
       }
       if (dedup::use_list(n_fresh, live_rounds, NM, p16_lds_bytes(n_pairs), (int)sizeof(DedupTail))) {
         list_rounds = dedup::list_rounds(n_fresh);
+        list_fresh = n_fresh;
         if (a.pathlen) {             // (test output) per ray, as the rounds write it: the rows go once round the register array
 #pragma unroll 1
           for (int q4 = 0; q4 < 4; ++q4) {
@@ -487,8 +551,14 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
   AirCache air_cache{0.0f, {0.0f, 0.0f}, false, {0.0f, 0.0f}};
   const size_t sstride_n = (size_t)a.n_local_views * a.g.n_rows * a.g.n_channels;
   const bool use_list = kDedup && list_rounds > 0;
+  // Narrow list rounds (dedup_index.h: round_rows; pa.det_dedup = 2: four rows per lane in every round, for the A/B).  A round costs
+  // what the rows of a lane cost, however few lanes have an entry, and the last round of a list is mostly short (an extruded wave:
+  // one entry per pair).  With at most 32 entries left for it, the last round detects two rows per lane, behind the loop of the
+  // four-row rounds.  The width is a function of the scalars list_fresh and list_rounds: the detection stays wave-uniform and its
+  // tables scalar operands.
+  const bool narrow_last = kNarrow && use_list && pa.det_dedup != 2 && dedup::round_rows(list_fresh, list_rounds - 1, kNarrowRows) == 2;
 #pragma unroll 1
-  for (int q4 = 0; q4 < (use_list ? list_rounds : 4); ++q4) {
+  for (int q4 = 0; q4 < (use_list ? list_rounds - (narrow_last ? 1 : 0) : 4); ++q4) {
     const bool round_live = lane_live && r0 + 4 * q4 < a.g.n_rows;
     if (!staged && !round_live) break;
     if (staged && !use_list && __ballot(round_live) == 0ull) break;          // wave-uniform: nobody has rows left
@@ -612,6 +682,47 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
     for (int m = 0; m < NM - 1; ++m)
 #pragma unroll
       for (int row = 0; row < 12; ++row) corr[m][row] = corr[m][row + 4];
+  }
+  // The narrow last round of a list (narrow_last, above), behind the four-row rounds and outside their loop: lane j detects the
+  // two rows 2 (j & 1), + 1 of entry 64 q4 + (j >> 1) - per ray the operations of the four-row form (detect_energies: each half
+  // of a pair runs the scalar sequence), half of the instructions.  A lane reads and writes its own half of every 16 bytes of its
+  // entry and nothing else.
+  if constexpr (kNarrow) {
+    if (narrow_last) {
+      const int q4 = list_rounds - 1;
+      uint8_t* entries = reinterpret_cast<uint8_t*>(lds_lists);
+      const DedupTail* tail = dedup_tail();
+      const int pair_end[4] = {tail->pair_end[0], tail->pair_end[1], tail->pair_end[2], tail->pair_end[3]};
+      const int e2 = dedup::lane_entry(2, q4, lane), first = dedup::lane_first_row(2, lane);
+      const bool e2_live = e2 < pair_end[3];
+      const float2 cl = tail->chord[e2_live ? dedup::entry_pair(e2, pair_end, n_pairs) : 0];
+      float2 sum2[NM - 1];
+#pragma unroll
+      for (int m = 0; m < NM - 1; ++m) {
+        sum2[m] = make_float2(0.0f, 0.0f);      // (lanes past the end of the list detect air, as in the four-row rounds)
+        if (e2_live) sum2[m] = *reinterpret_cast<const float2*>(entries + e2 * kEntry + dedup::piece_in(m, first));
+      }
+      float L[2][NM];
+#pragma unroll
+      for (int rr = 0; rr < 2; ++rr) {
+        float others = 0.0f;
+#pragma unroll
+        for (int m = 1; m < NM; ++m) others += rr ? sum2[m - 1].y : sum2[m - 1].x;
+        L[rr][0] = (cl.x - others) * cl.y;
+#pragma unroll
+        for (int m = 1; m < NM; ++m) L[rr][m] = (rr ? sum2[m - 1].y : sum2[m - 1].x) * cl.y;
+      }
+      const size_t rays2[2] = {0, 0};           // (the caller stores: detect_store looks at neither)
+      const bool valid2[2] = {true, true};
+      float res2[2][2];
+      __builtin_assume(a.n_spectra <= 2);        // (STAGED: the host's condition)
+      detect_store<NM, 2, false, false, kShort>(L, a, mu, w, w2, rays2, valid2, bm, nullptr, &res2);
+      if (e2_live) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+          *reinterpret_cast<float2*>(entries + e2 * kEntry + dedup::piece_out(s, first)) = make_float2(res2[s][0], res2[s][1]);
+      }
+    }
   }
   if constexpr (!staged) return;
   if constexpr (kDedup) {
@@ -806,7 +917,7 @@ static int packed_shape(const dexct_fan_geom* geom, int32_t view_begin, int32_t 
   pa.view_tile = proj::read_knob(proj::knob::kViewTileP16);
   pa.det_masks = proj::read_knob(proj::knob::kDetMasks) != 0;
   pa.det_absent = proj::read_knob(proj::knob::kDetAbsent) != 0;
-  pa.det_dedup = proj::read_knob(proj::knob::kDetDedup) != 0;
+  pa.det_dedup = proj::read_knob(proj::knob::kDetDedup);      // 0: off, 2: four-row list rounds only, else the narrow rounds too
   pa.view_begin = view_begin;
   const int n_pairs = 64 / pa.lanes_per_pair;
   if (!proj::grid_1d((size_t)(view_end - view_begin) * ((geom->n_channels + n_pairs - 1) / n_pairs) * pa.n_zchunks, grid))

@@ -29,6 +29,9 @@ n, views, chans = int(os.environ.get('N', 512)), int(os.environ.get('VIEWS', 100
 mode = sys.argv[1] if len(sys.argv) > 1 else 'census'
 ct = dx.FanBeamGeometry(N_channels=chans, N_proj=views, gamma_fan=0.8230337, SID=60.0, SDD=100.0, eid=True, detector_file=det, N_rows=n)
 specs = [synthetic.kramers_spectrum(140), synthetic.kramers_spectrum(80)]
+# A one-row round against a four-row round, per energy and lane, v_exp_f32 priced at two plain instructions: 5 v_fma_f32 + 1 v_exp_f32
+# = 7 against 10 v_pk_fma_f32 + 4 v_exp_f32 = 18 (three materials, two spectra)
+ONE_ROW = 7.0 / 18.0
 
 
 def volumes():
@@ -59,6 +62,8 @@ def census(name, ph, chunk=50):
     n_pairs = 64 // lpp
     assert n <= 1024 and n % 4 == 0 and chans % n_pairs == 0
     hist = torch.zeros(6, dtype=torch.int64, device='cuda')
+    last = torch.zeros(4, dtype=torch.int64, device='cuda')      # the last list round holds <= 16 / <= 32 / more entries; no list
+    eq = torch.zeros(3, dtype=torch.float64, device='cuda')      # round-equivalents: four-row rounds / two-row rule / one-row rule
     sum_f, extruded, waves = 0, 0, 0
     for vb in range(0, views, chunk):
         pj = fp.Projector(ct, ph, view_range=(vb, min(views, vb + chunk)))
@@ -69,6 +74,18 @@ def census(name, ph, chunk=50):
         f_pair = fresh.sum(dim=-1) + 1
         f = f_pair.reshape(pl.shape[0], chans // n_pairs, n_pairs).sum(dim=-1).reshape(-1)
         hist += torch.bincount((f + 63) // 64, minlength=6)[:6]
+        # the narrow rounds (csrc/dedup_index.h: round_rows): a wave detects its list where that saves a round (fewer than the
+        # four rounds of rows); every round of 64 entries is one round-equivalent, the last costs 1/2 at two rows per lane (at most
+        # 32 entries left) and ONE_ROW at one (at most 16)
+        rounds = (f + 63) // 64
+        left = f - 64 * (rounds - 1)
+        listed = rounds < 4
+        kind = torch.where(listed, torch.where(left <= 16, 0, torch.where(left <= 32, 1, 2)), 3)
+        last += torch.bincount(kind, minlength=4)
+        full = torch.where(listed, rounds, 4).double()
+        two = torch.where(listed & (left <= 32), full - 0.5, full)
+        one = torch.where(listed & (left <= 16), full - 1.0 + ONE_ROW, two)
+        eq += torch.stack([full.sum(), two.sum(), one.sum()])
         sum_f += int(f.sum())
         extruded += int((f == n_pairs).sum())
         waves += f.numel()
@@ -79,6 +96,12 @@ def census(name, ph, chunk=50):
     print(f'== census, {name}: {waves} waves of {quads} quads; mean F {sum_f / waves:.1f}; F = {n_pairs} (every pair extruded) in '
           f'{100.0 * extruded / waves:.1f} % of the waves', flush=True)
     print('   ceil(F / 64): ' + ', '.join(f'{k}: {100.0 * h / waves:.1f} %' for k, h in enumerate(hist) if h) + f'; mean {mean_rounds:.3f}', flush=True)
+    last, eq = last.cpu().tolist(), (eq / waves).cpu().tolist()
+    print('   entries left for the last list round: ' + ', '.join(f'{name}: {100.0 * h / waves:.1f} %' for name, h in
+                                                                   zip(('at most 16', '17 .. 32', '33 .. 64', 'no list (four rounds of rows)'), last)), flush=True)
+    print(f'   detection round-equivalents per wave: {eq[0]:.3f} with four-row rounds only, {eq[1]:.3f} with the last round at two rows '
+          f'for at most 32 entries (saves {eq[0] - eq[1]:.3f}), {eq[2]:.3f} with one row for at most 16 as well (at {ONE_ROW:.3f} of a round)',
+          flush=True)
 
 
 def timed(pj, mu_d, w_d, air, out, log, knob, reps=5):
