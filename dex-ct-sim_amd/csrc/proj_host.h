@@ -168,6 +168,10 @@ constexpr Knob kP16AirSkip{"DEXCT_P16_AIR_SKIP", 1, 0, 2};
 // against the air rule), 1 = used when use_class_map (proj_pure.h) says it pays, 2 = used whenever the caller passes one;
 // DEXCT_P16_AIR_SKIP = 0 turns it off with the air map
 constexpr Knob kP16Uniform{"DEXCT_P16_UNIFORM", 1, 0, 2};
+// rows16_kernel, the tile map of dexct_siddon_project_packed_tiles: 0 = never used (the class map serves alone: the A/B against
+// the slab rule), 1 = used when use_tile_map (proj_pure.h) says it pays, 2 = used whenever the caller passes one and the class
+// map is in use
+constexpr Knob kP16Tiles{"DEXCT_P16_TILES", 1, 0, 2};
 // cone row kernels, views per tile of the block order: 1 = all channels of a view before the next view (round 3: 9.6 ->
 // 9.2 ms on a 100-view scan, whose views 3.6 degrees apart share no columns; no difference at 0.36 degrees)
 constexpr Knob kConeViewTile{"DEXCT_CONE_VIEW_TILE", 1, 1, INT_MAX};

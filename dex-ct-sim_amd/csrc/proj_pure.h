@@ -49,5 +49,22 @@ inline bool use_class_map(int mode, int air_mode, bool have_map, const int64_t* 
   return droppable >= first;
 }
 
+// ---- the tile map (dexct_siddon_project_packed_tiles): whether a launch that uses the class map also dismisses runs by tiles.
+// mode: DEXCT_P16_TILES (knob::kP16Tiles) - 0 never, 1 when it pays, 2 whenever there is a tile map.  n_uniform[id]: tiles uniform
+// in id (class_counts_ok against the n_tiles tiles of the grid; impossible counts never use the map).  Measured on 512^3
+// (profiles/rows16_tiles.md): with 88 % of the tiles uniform (the benchmark phantom) the tile forms gain 0.52 ms of 3.76; with
+// 34 % (random blobs) they LOSE 0.07 ms of 19.5, with none (shuffled slices, class map forced) 0.23 ms of 34.7 - the run trips
+// and the dearer fine trips are not paid back; straight lines through neighbouring points break even at 40 % and 49 %.  So
+// mode 1 uses the map from kTileMapShareNum / kTileMapShareDen uniform tiles on.
+constexpr int64_t kTileMapShareNum = 1, kTileMapShareDen = 2;
+inline bool use_tile_map(int mode, bool have_map, const int64_t* n_uniform, int64_t n_tiles) {
+  if (!have_map || mode == 0 || !class_counts_ok(n_uniform, n_tiles)) return false;
+  if (mode == 2) return true;
+  const int64_t uniform = n_uniform[0] + n_uniform[1] + n_uniform[2] + n_uniform[3];      // <= n_tiles: class_counts_ok
+  const int64_t first = (n_tiles / kTileMapShareDen) * kTileMapShareNum +
+                        ((n_tiles % kTileMapShareDen) * kTileMapShareNum + kTileMapShareDen - 1) / kTileMapShareDen;
+  return uniform >= first;
+}
+
 }  // namespace proj
 }  // namespace dexct

@@ -69,6 +69,8 @@ struct PackedArgs {
     int sample;
     int col_class;
   };
+  // (the tile forms - noise-free, so they draw nothing either - read the seed's two words as the low and high half of the
+  // address of the tile map of dexct_volume_tile_classes, tile_class.h: for the same reason)
   uint32_t seed_lo, seed_hi;
   // air-column map (dexct_volume_air_columns): bit y * nx + x set = column (x, y) of vol_z2 is 0 over all z; the classification
   // enters no slab whose pieces inside the grid all lie in such columns.  Null: every slab is entered.

@@ -41,9 +41,12 @@
 #include "noise_sample.h"
 #include "proj_host.h"
 #include "sliced_count.h"
+#include "tile_class.h"
 #include "uniform_count.h"
 
 namespace dexct {
+
+static_assert(tiles::kFixFrac == DEXCT_FIX_FRAC, "the cells of a run are the cells of dda_slab");
 
 constexpr int kP16Super = 128;      // slabs staged per pass
 constexpr uint32_t kOob = 0xF0000000u;   // a list offset outside every buffer (< 3.75 GiB): the load returns 0 (air), no traffic
@@ -82,9 +85,16 @@ struct DedupTail {
 // a.variance (optional) receives the variances as well (tests; callers that sample with dexct_add_noise).
 // SKIP: the classification looks every slab up in the air-column map pa.col_air (dexct_siddon_project_packed_skip) and enters
 // no slab that lies in all-air columns; the forms without it are the kernels as they were.
-template <int NM, int MINW = 4, bool GROUPED = false, bool STAGED = false, bool NOISY = false, bool SKIP = false>      // MINW: waves per SIMD the register allocation must allow
-__global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const float* __restrict__ mu, const float* __restrict__ w,
+// TILES (the staged noise-free SKIP forms with a class map): runs of eight slabs whose tiles of the tile map (its address in
+// pa.seed_lo / pa.seed_hi) are uniform in one id are dismissed before any of their slabs is classified (tile_class.h).  The tile forms are the instantiations
+// with kTileForm added to MINW: a template parameter of their own would rename every other form of the kernel.
+constexpr int kTileForm = 16;
+template <int NM, int MINW_FORM = 4, bool GROUPED = false, bool STAGED = false, bool NOISY = false, bool SKIP = false>      // MINW: waves per SIMD the register allocation must allow
+__global__ __launch_bounds__(64, MINW_FORM % kTileForm) void rows16_kernel(PackedArgs pa, const float* __restrict__ mu, const float* __restrict__ w,
                                                     const float* __restrict__ w2) {
+  constexpr int MINW = MINW_FORM % kTileForm;
+  constexpr bool TILES = MINW_FORM >= kTileForm;
+  static_assert(MINW_FORM >= 1 && MINW_FORM < 2 * kTileForm && MINW >= 1 && MINW <= 8, "MINW_FORM is MINW (1 .. 8), or kTileForm + MINW");
   static_assert(NM >= 2 && NM <= 4, "ids 0..3");
   constexpr bool BOTH = NM > 3;              // id 3 exists: count the "both flags" plane too
   // detect_store<.., SHORT>: waves whose rays all miss the last material detect without it.  Not in the noisy three-material
@@ -162,7 +172,54 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
   // slabs they leave out, per id.  The other SKIP forms keep the air rule and the code they had (p16_by_class).
   constexpr bool kByClass = SKIP && p16_by_class(NM, STAGED, NOISY);
   uint32_t dropped = 0u;                     // this lane's dropped slabs (ucount::bump), over all passes
-  for (int s0 = 0; s0 < n_slabs_max; s0 += kP16Super) {
+  // TILES: the slabs are not taken 128 at a time.  Phase 1 (run trips, before the passes): a lane takes one RUN of its pair - the
+  // up to eight slabs of one tile row - finds the cells of its first and last piece (the cells between are the other pieces': j
+  // is monotone in the slab) and reads the at most three tiles they span, consecutive nibbles of one row of the tile map; a run
+  // whose tiles are all uniform in one id is dismissed and counted in `dropped` with all its slabs, which is what the slab rule
+  // would have done one slab at a time (tile_class.h has the argument).  One ballot per trip gives each pair's surviving runs; a
+  // ray has at most tiles::kWindow = 64 runs (the host launches these forms for grids up to 512 x 512 only), so a pair's
+  // surviving runs are ONE 64-bit mask, and the number of passes is known before the first: the pass loop stays a counted loop.
+  // (A pass loop that ended on the mask - runs left or not - cost the benchmark form 50 VGPRs spilled to scratch: the sums
+  // `corr` went to scratch round every classification.)  Phase 2 (passes): the next 16 surviving runs of every pair are 128 fine
+  // slabs, in slab order; lane li < 16 finds the li-th of them in the mask and fine slab f takes run f / 8 from that lane.  From
+  // there on the classification, the lists and the sweeps are those of the lean loop below: the same slabs reach the lists in
+  // the same order.
+  static_assert(!TILES || (SKIP && STAGED && !NOISY && kByClass), "the tile forms: staged, noise-free, with a class map");
+  [[maybe_unused]] unsigned long long alive_runs = 0ull;       // TILES: bit r = run r of this lane's pair survived
+  [[maybe_unused]] int n_passes = 0;
+  if constexpr (TILES) {
+    static_assert(tiles::kFineSlabs == kP16Super && tiles::kRunsPerPass <= 16, "a pass fills the lists; its runs fit a pair's lanes");
+    const tiles::Layout ty = tiles::layout((uint32_t)a.g.nx, (uint32_t)a.g.ny);
+    // Both words of a run are read through this bounds-checked buffer of exactly the map's words, each at its own VECTOR offset (the
+    // range check covers the vector and the immediate offset, not the scalar one).  A lane without a run (have == false: tile rows
+    // R >= ti, whose nibbles lie in or behind the spare word) and a plan that leaves the grid along the slab axis read behind the
+    // map: 0 without an access (tiles::checked_word on the host) - mixed, and the run of a lane that has one survives.
+    const __amdgpu_buffer_rsrc_t tile_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+        reinterpret_cast<uint32_t*>((uintptr_t)pa.seed_lo | (uintptr_t)pa.seed_hi << 32), 0, (int)(4u * ty.words), 0x00020000);
+    const uint32_t tj = axis == 0 ? ty.tj[0] : ty.tj[1], copy_at = axis == 0 ? ty.first_nibble[0] : ty.first_nibble[1];
+    const int R0 = tiles::first_run(p.i_first), n_runs = tiles::n_runs(p.i_first, p.n_slabs);
+    int n_runs_max = 0;
+    for (int k = 0; k < n_pairs; ++k) n_runs_max = max(n_runs_max, __builtin_amdgcn_readlane(n_runs, k * lpp));
+    for (int t0 = 0; t0 < tiles::kWindow && t0 < n_runs_max; t0 += lpp) {
+      const int r = t0 + li, R = R0 + r;
+      const bool have = r < n_runs;
+      const int i_lo = tiles::run_i_lo(R, p.i_first), i_hi = tiles::run_i_hi(R, p.i_first, p.n_slabs);
+      const int j0 = tiles::cell_of(p.V0, p.SV, i_lo), j1 = tiles::cell_of(p.V0, p.SV, i_hi + 1);
+      const int J_lo = tiles::tile_of_cell(min(j0, j1), tj), J_hi = tiles::tile_of_cell(max(j0, j1), tj);
+      const uint32_t nib = tiles::nibble_at(copy_at, tj, (uint32_t)R, J_lo);
+      const uint32_t w_lo = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(tile_rsrc, (int)(tiles::word_of_nibble(nib) << 2), 0, 0);
+      const uint32_t w_hi = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(tile_rsrc, (int)((tiles::word_of_nibble(nib) + 1u) << 2), 0, 0);
+      const uint32_t e = tiles::dismissed_in(tiles::nibbles_from(w_lo, w_hi, nib), J_hi - J_lo + 1);
+      dropped += have ? tiles::bump_run(e, i_hi - i_lo + 1) : 0u;
+      const unsigned long long alive = __ballot(have && e == 0u);
+      alive_runs |= ((alive & group_mask) >> (g * lpp)) << t0;
+    }
+    int most = 0;
+    for (int k = 0; k < n_pairs; ++k) most = max(most, __builtin_amdgcn_readlane((int)__popcll(alive_runs), k * lpp));
+    n_passes = (most + tiles::kRunsPerPass - 1) / tiles::kRunsPerPass;
+  }
+  // a pass: the next 128 slabs of the wave's rays - TILES: the next 16 surviving runs of its pairs
+  for (int s0 = 0; s0 < (TILES ? n_passes * kP16Super : n_slabs_max); s0 += kP16Super) {
     // ---- geometry: the lanes of a pair classify its slabs s0 + li, s0 + li + lpp, ... (slab order kept per pair)
     int run_f = 0, run_c = 0;               // per pair (identical in all lanes of a pair)
     // SKIP: the same classification as below, kAirBatch iterations at a time so that their map words are in
@@ -187,7 +244,57 @@ __global__ __launch_bounds__(64, MINW) void rows16_kernel(PackedArgs pa, const f
     //     grid classes as air through ina / inb as before, never through the word.
     //   - The offsets col x zb are formed only where a slab is written to a list.
     constexpr bool kLeanClass = SKIP && STAGED && !NOISY;
-    if constexpr (kLeanClass) {
+    if constexpr (TILES) {
+      const uint32_t cu = axis == 0 ? 1u : (uint32_t)a.g.nx, cv = axis == 0 ? (uint32_t)a.g.nx : 1u;
+      constexpr ucount::MapKind mk = ucount::map_kind(true);
+      const __amdgpu_buffer_rsrc_t map_rsrc = __builtin_amdgcn_make_buffer_rsrc(
+          const_cast<uint32_t*>(pa.col_air), 0, (int)(4u * ucount::map_words((uint32_t)a.g.nx * (uint32_t)a.g.ny, mk)), 0x00020000);
+      // the pass's runs: lane li < 16 holds the li-th of them, by its rank among the pair's surviving runs (64: none)
+      const int first = tiles::kRunsPerPass * (s0 / kP16Super);
+      const int n_mine = min(tiles::kRunsPerPass, max(0, (int)__popcll(alive_runs) - first));
+      const int mine = li < n_mine ? tiles::surviving_run(alive_runs, first + li) : tiles::kWindow;
+      int n_taken = 0;
+      for (int k = 0; k < n_pairs; ++k) n_taken = max(n_taken, __builtin_amdgcn_readlane(n_mine, k * lpp));
+      const int q_end = min(kP16Super, (tiles::kSide * n_taken + kAirBatch * lpp - 1) & ~(kAirBatch * lpp - 1));
+      for (int q0 = 0; q0 < q_end; q0 += kAirBatch * lpp) {
+        uint32_t cola[kAirBatch], colb[kAirBatch], wa[kAirBatch], wb[kAirBatch];
+        float tt[kAirBatch];
+        bool ina[kAirBatch], inb[kAirBatch], one[kAirBatch];
+#pragma unroll
+        for (int u = 0; u < kAirBatch; ++u) {
+          // fine slab f of the pass: slab f % 8 of the pair's (f / 8)-th run; the rest is the lean loop's
+          const int f = q0 + u * lpp + li;
+          const int run = __shfl(mine, g * lpp + tiles::fine_rank(f));
+          const int i = ((tiles::first_run(p.i_first) + run) << tiles::kShift) + tiles::fine_slab(f);
+          const bool have = tiles::fine_rank(f) < n_mine && (uint32_t)(i - p.i_first) < (uint32_t)p.n_slabs;
+          const SlabPieces sp = dda_slab((long long)((unsigned long long)p.V0 + (unsigned long long)((long long)i * p.SV)), p.SV, smask, p.kf);
+          ina[u] = have && (uint32_t)sp.ja < (uint32_t)nv;
+          inb[u] = have && (uint32_t)sp.jb < (uint32_t)nv;
+          const uint32_t icu = __umul24((uint32_t)i, cu);
+          cola[u] = icu + __umul24((uint32_t)sp.ja, cv);
+          colb[u] = icu + __umul24((uint32_t)sp.jb, cv);
+          one[u] = sp.ja == sp.jb;
+          tt[u] = sp.t;
+          wa[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(map_rsrc, (int)(ucount::word_of(cola[u], mk) << 2), 0, 0);
+          wb[u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(map_rsrc, (int)(ucount::word_of(colb[u], mk) << 2), 0, 0);
+        }
+#pragma unroll
+        for (int u = 0; u < kAirBatch; ++u) {
+          const uint32_t ea = ina[u] ? ucount::class_in(wa[u], cola[u], mk) : ucount::kAirClass;
+          const uint32_t eb = inb[u] ? ucount::class_in(wb[u], colb[u], mk) : ucount::kAirClass;
+          const bool keep = !ucount::droppable(ea, eb);
+          dropped += keep ? 0u : ucount::bump(eb);
+          const bool whole = ina[u] && inb[u] && one[u];
+          const bool is_full = whole && keep, is_cross = !whole && (ina[u] || inb[u]) && keep;
+          const unsigned long long mf = __ballot(is_full), mc = __ballot(is_cross);
+          if (is_full) list_full[g][run_f + __popcll(mf & below_mask)] = colb[u] * zb;
+          if (is_cross)
+            list_cross[g][run_c + __popcll(mc & below_mask)] = CrossRec{ina[u] ? cola[u] * zb : kOob, inb[u] ? colb[u] * zb : kOob, tt[u], 0u};
+          run_f += __popcll(mf & group_mask);
+          run_c += __popcll(mc & group_mask);
+        }
+      }
+    } else if constexpr (kLeanClass) {
       const uint32_t cu = axis == 0 ? 1u : (uint32_t)a.g.nx, cv = axis == 0 ? (uint32_t)a.g.nx : 1u;
       const ucount::MapKind mk = ucount::map_kind(pa.col_class != 0);       // (wave-uniform)
       const __amdgpu_buffer_rsrc_t map_rsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -861,6 +968,25 @@ __global__ __launch_bounds__(256) void col_class_kernel(const uint8_t* __restric
   }
 }
 
+// The tile map of a column-class map (tile_class.h, include/dexct_p16_tiles.h): one thread per nibble of either copy, the outside
+// tiles in front of and behind every row included; the map was cleared before, and the eight threads of a word OR their nibbles
+// into it.  n_uniform[id] receives the uniform tiles of the grid per id, counted in copy 1 (both copies hold the same tiles).
+__global__ __launch_bounds__(256) void tile_class_kernel(const uint32_t* __restrict__ col_class, uint32_t nx, uint32_t ny,
+                                                         uint32_t* __restrict__ tile_map, unsigned long long* __restrict__ n_uniform) {
+  const tiles::Layout y = tiles::layout(nx, ny);
+  const uint32_t per_copy[2] = {y.ti[0] * tiles::row_nibbles(y.tj[0]), y.ti[1] * tiles::row_nibbles(y.tj[1])};
+  for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < per_copy[0] + per_copy[1]; k += gridDim.x * 256u) {
+    const int axis = k < per_copy[0] ? 0 : 1;
+    const uint32_t at = k - (axis ? per_copy[0] : 0u), row = tiles::row_nibbles(y.tj[axis]);
+    const uint32_t I = at / row;
+    const int32_t J = (int32_t)(at - I * row) - 1;
+    const uint32_t e = tiles::class_of_nibble(col_class, nx, ny, axis, I, J);
+    const uint32_t nib = tiles::nibble_of(y, axis, I, J);
+    if (e) atomicOr(tile_map + tiles::word_of_nibble(nib), e << ((nib & 7u) << 2));
+    if (e && axis == 1 && J >= 0 && J < (int32_t)y.tj[1]) atomicAdd(n_uniform + (e >> 1), 1ull);
+  }
+}
+
 // the grid cap of col_air_kernel and col_class_kernel (one column per thread)
 constexpr int kColAirMaxBlocks = 4096;
 
@@ -891,6 +1017,11 @@ struct P16Launch {
   hipStream_t st;
   bool staged_store;      // DEXCT_P16_STAGED: store the results of a wave through LDS as whole lines (0: per-round 16-B stores)
 };
+// TWO ENCODINGS to know before adding a form (both keep every other form's name and PackedArgs as they were):
+//  - MINW here is the kernel's MINW_FORM: the waves per SIMD (1 .. 8), plus kTileForm for a tile form (launch_p16_tiles is the only
+//    caller that adds it; a value of DEXCT_P16_MINW never reaches this parameter - the entry point maps it to 4, 5, 6 or 8);
+//  - a tile form reads l.pa.seed_lo / seed_hi as the address of the tile map.  The noisy forms read the same words as the seed of
+//    their sample, so a noisy tile form needs a place of its own for one of the two (the kernel asserts that TILES excludes NOISY).
 template <int NM, int MINW, bool GROUPED, bool STAGED, bool NOISY, bool SKIP = false>
 static int launch_p16(const P16Launch& l) {
   hipLaunchKernelGGL((rows16_kernel<NM, MINW, GROUPED, STAGED, NOISY, SKIP>), l.grid, dim3(64), l.lds, l.st, l.pa, l.t.mu, l.t.w, l.t.w2);
@@ -936,6 +1067,12 @@ static int launch_p16_skip(const P16Launch& l, int n_materials, bool staged, boo
   if (n_materials == 2) return staged ? launch_p16<2, 4, false, true, false, true>(l) : launch_p16<2, 4, false, false, false, true>(l);
   if (n_materials == 4) return staged ? launch_p16<4, 3, false, true, false, true>(l) : launch_p16<4, 3, false, false, false, true>(l);
   return staged ? launch_p16<3, 4, false, true, false, true>(l) : launch_p16<3, 4, false, false, false, true>(l);
+}
+// the tile forms: the staged noise-free SKIP forms with kTileForm added to their MINW (the tile map's address and a class map are set)
+static int launch_p16_tiles(const P16Launch& l, int n_materials) {
+  if (n_materials == 2) return launch_p16<2, kTileForm + 4, false, true, false, true>(l);
+  if (n_materials == 4) return launch_p16<4, kTileForm + 3, false, true, false, true>(l);
+  return launch_p16<3, kTileForm + 4, false, true, false, true>(l);
 }
 
 }  // namespace dexct
@@ -996,6 +1133,27 @@ int dexct_volume_column_classes(const uint8_t* vol_z2, int32_t nx, int32_t ny, i
   return DEXCT_OK;
 }
 
+int64_t dexct_volume_tile_map_words(int32_t nx, int32_t ny) {
+  if (nx < 1 || ny < 1 || (uint64_t)nx * ny > 0x7FFFFF00ull) return 0;
+  return tiles::layout((uint32_t)nx, (uint32_t)ny).words;
+}
+
+int dexct_volume_tile_classes(const uint32_t* col_class, int32_t nx, int32_t ny, uint32_t* tile_map, uint64_t* n_uniform, void* stream) {
+  if (!col_class || !tile_map || !n_uniform || nx < 1 || ny < 1) return DEXCT_EINVAL;
+  if ((uint64_t)nx * ny > 0x7FFFFF00ull) return DEXCT_ERANGE;
+  const tiles::Layout y = tiles::layout((uint32_t)nx, (uint32_t)ny);
+  hipStream_t st = as_stream(stream);
+  DEXCT_HIP_TRY(hipMemsetAsync(n_uniform, 0, 4 * sizeof(uint64_t), st));
+  DEXCT_HIP_TRY(hipMemsetAsync(tile_map, 0, (size_t)y.words * sizeof(uint32_t), st));
+  const uint32_t n_nibbles = y.ti[0] * tiles::row_nibbles(y.tj[0]) + y.ti[1] * tiles::row_nibbles(y.tj[1]);
+  uint32_t nblk = (n_nibbles + 255u) / 256u;
+  if (nblk > (uint32_t)kColAirMaxBlocks) nblk = kColAirMaxBlocks;
+  hipLaunchKernelGGL(tile_class_kernel, dim3(nblk), dim3(256), 0, st, col_class, (uint32_t)nx, (uint32_t)ny, tile_map,
+                     reinterpret_cast<unsigned long long*>(n_uniform));
+  DEXCT_LAUNCH_CHECK();
+  return DEXCT_OK;
+}
+
 int dexct_siddon_project_packed(const dexct_fan_geom* geom, const dexct_ray_plan* plan, int32_t view_begin,
                                 int32_t view_end, const uint8_t* vol_z2, int32_t n_materials, int32_t n_energies,
                                 int32_t n_spectra, const float* mu, const float* weights, float* counts, float* pathlen,
@@ -1021,6 +1179,18 @@ int dexct_siddon_project_packed_uniform(const dexct_fan_geom* geom, const dexct_
                                         int32_t layout, const dexct_log_out* log_out, const float* weights2, float* variance,
                                         const dexct_noise* noise, const uint32_t* col_air, int64_t n_air_columns,
                                         const uint32_t* col_class, const int64_t* n_uniform_columns, void* stream) {
+  return dexct_siddon_project_packed_tiles(geom, plan, view_begin, view_end, vol_z2, n_materials, n_energies, n_spectra, mu, weights,
+                                           counts, pathlen, layout, log_out, weights2, variance, noise, col_air, n_air_columns,
+                                           col_class, n_uniform_columns, nullptr, nullptr, stream);
+}
+
+int dexct_siddon_project_packed_tiles(const dexct_fan_geom* geom, const dexct_ray_plan* plan, int32_t view_begin,
+                                      int32_t view_end, const uint8_t* vol_z2, int32_t n_materials, int32_t n_energies,
+                                      int32_t n_spectra, const float* mu, const float* weights, float* counts, float* pathlen,
+                                      int32_t layout, const dexct_log_out* log_out, const float* weights2, float* variance,
+                                      const dexct_noise* noise, const uint32_t* col_air, int64_t n_air_columns,
+                                      const uint32_t* col_class, const int64_t* n_uniform_columns, const uint32_t* tile_map,
+                                      const int64_t* n_uniform_tiles, void* stream) {
   if (!geom || !plan || !vol_z2 || !mu || !weights || !counts) return DEXCT_EINVAL;
   if (n_energies < 1 || n_spectra < 1) return DEXCT_EINVAL;
   if (n_materials < 2 || n_materials > 4 || n_spectra > DEXCT_MAX_SPECTRA) return DEXCT_ERANGE;     // ids 0..3
@@ -1061,6 +1231,16 @@ int dexct_siddon_project_packed_uniform(const dexct_fan_geom* geom, const dexct_
   else l.pa.col_air = proj::use_air_map(air_mode, col_air != nullptr, n_air_columns, n_cols) ? col_air : nullptr;
   proj::copy_noise(l.pa, view_begin, nl);     // (rows16_kernel draws the sample itself: PackedArgs, not its ProjArgs)
   if (!noisy) l.pa.col_class = by_class ? 1 : 0;      // (the word is `sample` to the noisy forms)
+  // the tile map rides on the class map, in the staged forms that take one (the words are the seed to the noisy forms)
+  const int64_t n_tiles = (int64_t)tiles::tiles_along((uint32_t)geom->nx) * tiles::tiles_along((uint32_t)geom->ny);
+  if (tile_map && (!n_uniform_tiles || !proj::class_counts_ok(n_uniform_tiles, n_tiles))) return DEXCT_EINVAL;
+  const bool by_tiles = by_class && skip_staged && !minw_form && tiles::grid_fits((uint32_t)geom->nx, (uint32_t)geom->ny) &&
+                        proj::use_tile_map(proj::read_knob(proj::knob::kP16Tiles), tile_map != nullptr, n_uniform_tiles, n_tiles);
+  if (by_tiles) {
+    l.pa.seed_lo = (uint32_t)reinterpret_cast<uintptr_t>(tile_map);      // (PackedArgs: the seed's words, which these forms do not draw from)
+    l.pa.seed_hi = (uint32_t)(reinterpret_cast<uintptr_t>(tile_map) >> 32);
+    return launch_p16_tiles(l, n_materials);
+  }
   // with a map: the SKIP forms, which exist for the default MINW only
   if (l.pa.col_air && !minw_form) return launch_p16_skip(l, n_materials, skip_staged, noisy);
   if (noisy) {

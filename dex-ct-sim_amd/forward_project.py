@@ -198,6 +198,7 @@ class Projector:
                                                     ptr(self.vol_xy), ptr(self.vol_zf), st), 'dexct_volume_layouts')
         self.vol_z2, self.col_air, self.n_air_columns = None, None, 0
         self.col_class, self.n_uniform_columns = None, [0, 0, 0, 0]
+        self.tile_map, self.n_uniform_tiles = None, [0, 0, 0, 0]
         if self.use_packed:
             self.vol_z2 = torch.empty(self.vol_zf.numel() // 4, dtype=torch.uint8, device=self.dev)
             _native.check(self.lib.dexct_volume_pack2(ptr(self.vol_zf), self.vol_zf.numel(), ptr(self.vol_z2), st),
@@ -216,6 +217,12 @@ class Projector:
             _native.check(self.lib.dexct_volume_column_classes(ptr(self.vol_z2), phantom.Nx, phantom.Ny, nz, ptr(self.col_class),
                                                                ptr(n_uniform), st), 'dexct_volume_column_classes')
             self.n_uniform_columns = [int(k) for k in n_uniform.tolist()]
+            # the tile map of that class map (four bits per 8 x 8 columns) and the uniform tiles per id: the kernel dismisses
+            # the runs of slabs that stay inside uniform tiles before it classifies slabs one by one
+            self.tile_map = torch.empty(self.lib.dexct_volume_tile_map_words(phantom.Nx, phantom.Ny), dtype=torch.int32, device=self.dev)
+            _native.check(self.lib.dexct_volume_tile_classes(ptr(self.col_class), phantom.Nx, phantom.Ny, ptr(self.tile_map),
+                                                             ptr(n_uniform), st), 'dexct_volume_tile_classes')
+            self.n_uniform_tiles = [int(k) for k in n_uniform.tolist()]
         # ---- 6. group codes of the material-group passes
         aligned = nz % 4 == 0 and z_first % 4 == 0
         self.grouped = not self.grouped_packed and (kernel == 4 or (kernel == 0 and row_parallel and M > 4 and aligned))
@@ -442,10 +449,11 @@ class Projector:
                 geom, c.plan_ptr, *self._cone_rays(), c.vb, ve, ptr(self.vol_yx), ptr(self.vol_xy), M, c.nE, c.S, c.mu, c.w,
                 ptr(counts), ptr(pathlen), lo, c.w2, ptr(variance), c.nz, stream_ptr()), 'dexct_cone_project')
         elif c.packed:                                          # (noise on > 2 spectra: the byte-volume kernel below)
-            _native.check(lib.dexct_siddon_project_packed_uniform(
+            _native.check(lib.dexct_siddon_project_packed_tiles(
                 geom, c.plan_ptr, c.vb, ve, ptr(self.vol_z2), M, c.nE, c.S, c.mu, c.w, ptr(counts), ptr(pathlen), c.run_layout, lo,
                 c.w2, ptr(variance), c.nz, ptr(self.col_air), self.n_air_columns, ptr(self.col_class),
-                (C.c_int64 * 4)(*self.n_uniform_columns), stream_ptr()), 'dexct_siddon_project_packed_uniform')
+                (C.c_int64 * 4)(*self.n_uniform_columns), ptr(self.tile_map), (C.c_int64 * 4)(*self.n_uniform_tiles),
+                stream_ptr()), 'dexct_siddon_project_packed_tiles')
         else:
             _native.check(lib.dexct_siddon_project(
                 geom, c.plan_ptr, c.vb, ve, ptr(self.vol_yx), ptr(self.vol_xy), ptr(self.vol_zf), M, c.nE, c.S, c.mu, c.w,

@@ -834,5 +834,6 @@ int dexct_pwls_update(const float* x_old, const float* g, const float* d, int32_
 
 #include "dexct_gn_dedup.h"      /* additive to ABI 6: the Newton decomposition that solves repeated rows once */
 #include "dexct_p16_uniform.h"   /* additive to ABI 6: the column-class map and the packed projection that uses it */
+#include "dexct_p16_tiles.h"     /* additive to ABI 6: the tile map of a column-class map and the packed projection that uses it */
 
 #endif /* DEXCT_H */
