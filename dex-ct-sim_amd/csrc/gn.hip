@@ -283,67 +283,142 @@ __host__ __device__ inline size_t gn_ws_tables_bytes(int n_e, int n_bins) {
 // One block per spectrum row ("bin": 1 for the channel-independent case, else one per detector channel).
 // i0 is [2][n_bins][n_e].  With several bins the energies are NOT sorted into classes (they may differ
 // per bin): class A then simply holds all n_e energies.
-__global__ __launch_bounds__(256) void gn_tables_kernel(const double* __restrict__ i0, const double* __restrict__ mus,
-                                                        int n_e, int n_bins, double* __restrict__ ws) {
+// Every thread classes its own energies (256 per trip of the block, n_e is not bounded): the class of an energy is which
+// spectra weight it and whether its attenuation is above kMuFree, the stable partition comes from block-wide counts (ballots
+// per wave, the waves' counts through LDS), m0f / m1f are maximum reductions (exact, in any order).  Only the two sums that set
+// the scale keep one thread and their order; they read a copy staged in LDS.  (One thread walking the energies seven times
+// through global memory took 0.10 ms in front of every Newton call, profiles/gn_route_streaming.md.)
+constexpr int kTabBlock = 256, kTabWaves = kTabBlock / kWave, kTabKeys = 6;      // key = 2 * class + (0: clip always, 1: the rest)
+
+// the key of energy e; kTabKeys: no spectrum weights it (or e is beyond the last energy)
+__device__ __forceinline__ int gn_energy_key(const double* __restrict__ i00, const double* __restrict__ i01, const double* __restrict__ mus,
+                                             int n_e, int e, double* m0, double* m1) {
+  // kMuFree = 4 cm^2/g keeps the bound valid up to |a0| + |a1| = 175 g/cm^2, far beyond any physical ray
+  const double kMuFree = 4.0;
+  if (e >= n_e) return kTabKeys;
+  const bool z0 = i00[e] == 0.0, z1 = i01[e] == 0.0;
+  const int c = (!z0 && !z1) ? 0 : (!z0 ? 1 : (!z1 ? 2 : 3));
+  *m0 = fabs(mus[e]);
+  *m1 = fabs(mus[n_e + e]);
+  const bool big = !(fmax(*m0, *m1) <= kMuFree);
+  return c == 3 ? kTabKeys : 2 * c + (big ? 0 : 1);
+}
+
+__global__ __launch_bounds__(kTabBlock) void gn_tables_kernel(const double* __restrict__ i0, const double* __restrict__ mus,
+                                                              int n_e, int n_bins, double* __restrict__ ws) {
   // float32 tables are scaled by one power of two common to both measurements (the Newton step is
   // invariant under a common scaling of counts and spectra) so that sums stay near 1.
   __shared__ double s_scale;
   __shared__ int s_n[3], s_nc[3];
-  const int bin = blockIdx.x;
+  __shared__ double s_stage[2][kTabBlock];              // a trip's weights, for the ordered sums
+  __shared__ int s_cnt[kTabWaves][kTabKeys];            // a wave's energies per key: of all trips, then of one trip
+  __shared__ double s_max[kTabWaves][2];
+  const int bin = blockIdx.x, t = threadIdx.x, wv = t >> 6, lane = t & 63;
   const double* __restrict__ i00 = i0 + (size_t)bin * n_e;                       // k = 0
   const double* __restrict__ i01 = i0 + ((size_t)n_bins + bin) * n_e;            // k = 1
   double* tab = ws + kWsHeader + (size_t)bin * n_e * kTab;
   float* tab32 = reinterpret_cast<float*>(ws + kWsHeader + (size_t)n_bins * n_e * kTab);   // only for n_bins == 1
   int* perm = reinterpret_cast<int*>(tab32 + (size_t)n_e * kTab) + (size_t)bin * n_e;
-  if (threadIdx.x == 0) {
-    double s0 = 0.0, s1 = 0.0;
-    for (int e = 0; e < n_e; ++e) { s0 += i00[e]; s1 += i01[e]; }
+  double s0 = 0.0, s1 = 0.0;                            // (thread 0's)
+  for (int e0 = 0; e0 < n_e; e0 += kTabBlock) {
+    if (e0 + t < n_e) { s_stage[0][t] = i00[e0 + t]; s_stage[1][t] = i01[e0 + t]; }
+    __syncthreads();
+    if (t == 0) {
+      const int n = n_e - e0 < kTabBlock ? n_e - e0 : kTabBlock;
+      for (int j = 0; j < n; ++j) { s0 += s_stage[0][j]; s1 += s_stage[1][j]; }
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
     int ex = 0;
     frexp(fmax(s0, s1), &ex);
     s_scale = ldexp(1.0, -ex);
-    int n = 0;
-    double m0f = 0.0, m1f = 0.0;
-    if (n_bins == 1) {
-      // stable partition of the energies into the classes A (both), B (only 0), C (only 1), each split into
-      // [large attenuation: clip always | the rest]; kMuFree = 4 cm^2/g keeps the bound valid up to
-      // |a0| + |a1| = 175 g/cm^2, far beyond any physical ray
-      const double kMuFree = 4.0;
-      for (int cls = 0; cls < 3; ++cls) {
-        for (int part = 0; part < 2; ++part) {
-          int cnt = 0;
-          for (int e = 0; e < n_e; ++e) {
-            const bool z0 = i00[e] == 0.0, z1 = i01[e] == 0.0;
-            const int c = (!z0 && !z1) ? 0 : (!z0 ? 1 : (!z1 ? 2 : 3));
-            const bool big = !(fmax(fabs(mus[e]), fabs(mus[n_e + e])) <= kMuFree);
-            if (c == cls && big == (part == 0)) {
-              perm[n++] = e;
-              ++cnt;
-              if (!big) { m0f = fmax(m0f, fabs(mus[e])); m1f = fmax(m1f, fabs(mus[n_e + e])); }
-            }
-          }
-          if (part == 0) s_nc[cls] = cnt; else s_n[cls] = s_nc[cls] + cnt;
-        }
+  }
+  double m0f = 0.0, m1f = 0.0;
+  if (n_bins == 1) {
+    // stable partition of the energies into the classes A (both), B (only 0), C (only 1), each split into
+    // [large attenuation: clip always | the rest]: how many energies each key has, then every energy's place
+    int cnt[kTabKeys];                                  // wave-uniform
+#pragma unroll
+    for (int k = 0; k < kTabKeys; ++k) cnt[k] = 0;
+    for (int e0 = 0; e0 < n_e; e0 += kTabBlock) {
+      double m0 = 0.0, m1 = 0.0;
+      const int key = gn_energy_key(i00, i01, mus, n_e, e0 + t, &m0, &m1);
+#pragma unroll
+      for (int k = 0; k < kTabKeys; ++k) cnt[k] += (int)__popcll(__ballot(key == k));
+      if (key < kTabKeys && (key & 1)) { m0f = fmax(m0f, m0); m1f = fmax(m1f, m1); }
+    }
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+      m0f = fmax(m0f, __shfl_xor(m0f, d));
+      m1f = fmax(m1f, __shfl_xor(m1f, d));
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < kTabKeys; ++k) s_cnt[wv][k] = cnt[k];
+      s_max[wv][0] = m0f;
+      s_max[wv][1] = m1f;
+    }
+    __syncthreads();
+    int run[kTabKeys], n = 0;                           // where the next energy of a key goes: block-uniform
+#pragma unroll
+    for (int k = 0; k < kTabKeys; ++k) {
+      run[k] = n;
+      for (int w = 0; w < kTabWaves; ++w) n += s_cnt[w][k];
+    }
+    for (int w = 0; w < kTabWaves; ++w) { m0f = fmax(m0f, s_max[w][0]); m1f = fmax(m1f, s_max[w][1]); }
+    if (t == 0) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        s_nc[c] = run[2 * c + 1] - run[2 * c];
+        s_n[c] = (c < 2 ? run[2 * c + 2] : n) - run[2 * c];
       }
-    } else {
-      for (int e = 0; e < n_e; ++e) perm[e] = e;
+    }
+    for (int e0 = 0; e0 < n_e; e0 += kTabBlock) {
+      __syncthreads();                                  // (s_cnt: read above and by the trip before)
+      double m0, m1;
+      const int key = gn_energy_key(i00, i01, mus, n_e, e0 + t, &m0, &m1);
+      int below = 0;                                    // this key's energies in the lanes below
+#pragma unroll
+      for (int k = 0; k < kTabKeys; ++k) {
+        const unsigned long long m = __ballot(key == k);
+        if (lane == 0) s_cnt[wv][k] = (int)__popcll(m);
+        if (key == k) below = (int)__popcll(m & ((1ull << lane) - 1ull));
+      }
+      __syncthreads();
+#pragma unroll
+      for (int k = 0; k < kTabKeys; ++k) {
+        int before = 0, all = 0;
+        for (int w = 0; w < kTabWaves; ++w) {
+          const int c = s_cnt[w][k];
+          before += w < wv ? c : 0;
+          all += c;
+        }
+        if (key == k) perm[run[k] + before + below] = e0 + t;
+        run[k] += all;
+      }
+    }
+  } else {
+    for (int e = t; e < n_e; e += kTabBlock) perm[e] = e;
+    if (t == 0) {
       s_n[0] = n_e; s_n[1] = 0; s_n[2] = 0;
       s_nc[0] = n_e; s_nc[1] = 0; s_nc[2] = 0;      // channel-dependent spectra: everything clipped
     }
-    if (bin == 0) {
-      ws[0] = s_scale;
-      ws[1] = (double)s_n[0];
-      ws[2] = (double)s_n[1];
-      ws[3] = (double)s_n[2];
-      ws[4] = (double)s_nc[0];
-      ws[5] = (double)s_nc[1];
-      ws[6] = (double)s_nc[2];
-      ws[7] = m0f;
-      ws[8] = m1f;
-      reinterpret_cast<unsigned long long*>(ws)[kWsExecuted] = 0ull;      // executed pixel-iterations, counted by gn_refill_kernel
-      reinterpret_cast<unsigned long long*>(ws)[kWsProgress] = 0ull;      // finished pixels (progress of the running launch)
-      reinterpret_cast<unsigned long long*>(ws)[kWsQueueHead] = 0ull;     // head of the tile queue of gn_refill_kernel
-      reinterpret_cast<unsigned long long*>(ws)[kWsStalls] = 0ull;        // lane-steps stalled on result slots
-    }
+  }
+  if (t == 0 && bin == 0) {
+    ws[0] = s_scale;
+    ws[1] = (double)s_n[0];
+    ws[2] = (double)s_n[1];
+    ws[3] = (double)s_n[2];
+    ws[4] = (double)s_nc[0];
+    ws[5] = (double)s_nc[1];
+    ws[6] = (double)s_nc[2];
+    ws[7] = m0f;
+    ws[8] = m1f;
+    reinterpret_cast<unsigned long long*>(ws)[kWsExecuted] = 0ull;      // executed pixel-iterations, counted by gn_refill_kernel
+    reinterpret_cast<unsigned long long*>(ws)[kWsProgress] = 0ull;      // finished pixels (progress of the running launch)
+    reinterpret_cast<unsigned long long*>(ws)[kWsQueueHead] = 0ull;     // head of the tile queue of gn_refill_kernel
+    reinterpret_cast<unsigned long long*>(ws)[kWsStalls] = 0ull;        // lane-steps stalled on result slots
   }
   if (bin == 0) {                       // the histogram of the tile sort starts at zero
     int* hist = reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + gn_ws_tables_bytes(n_e, n_bins));
@@ -653,6 +728,14 @@ __device__ __forceinline__ long long gn_uniform(long long t) {      // lane 0's 
 }
 __device__ __forceinline__ int gn_batch(int flags) {         // tiles per queue reservation, at least 1
   return ((flags >> kFlagFetchShift) & kFlagFetchMask) > 0 ? ((flags >> kFlagFetchShift) & kFlagFetchMask) : 1;
+}
+// Whether the tile queue is used up already when a block starts.  The dedup route launches its pass twice - on the list and on
+// the sinograms - and the device decides which of the two has work by where it puts the head; the head only grows during a
+// launch, so a block that sees it at the end has nothing to do and leaves before it fills lds_pow and sends an atomic per wave
+// to the one queue word (0.10 ms of 4096 atomics, profiles/gn_route_streaming.md).  Every other call starts at 0 and pays this load.
+__device__ __forceinline__ bool gn_queue_used_up(unsigned long long* counters, long long n_tiles) {
+  const unsigned long long head = __hip_atomic_load(gn_counter(counters, kWsQueueHead), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return gn_uniform((long long)head) >= n_tiles;
 }
 __device__ __forceinline__ const int* gn_tile_order(const unsigned long long* counters, int n_e) {      // counters = workspace word kWsExecuted; shared-spectrum kernels: n_bins = 1
   return reinterpret_cast<const int*>(reinterpret_cast<const char*>(counters - kWsExecuted) + gn_ws_tables_bytes(n_e, 1)) + kSortBuckets;
@@ -1046,6 +1129,7 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_refill_kernel(const void* __re
   __shared__ d2 lds_out[kGnBlock / kWave][kSlots * kTilePix];            // 12 KB: with the table 28 KB = 5 workgroups per CU
   __shared__ unsigned char lds_it[COUNT ? kGnBlock / kWave : 1][COUNT ? kSlots * kTilePix : 1];
   unsigned char* __restrict__ my_it = lds_it[COUNT ? (threadIdx.x >> 6) : 0];
+  if (!COUNT && gn_queue_used_up(counters, tl.n_tiles)) return;          // (the dedup route's launch without work)
   // the loop of exptab::fill_pow_table, kept as text: the call compiles to another instruction order (tools/device_asm_diff.py)
   for (int j = threadIdx.x; j < kPowN; j += kGnBlock) lds_pow[j] = pow_entry(j);
   __syncthreads();                        // the only barrier: waves leave the loop below independently
@@ -1238,6 +1322,7 @@ __global__ __launch_bounds__(kGnBlock, 4) void gn_shortcut_kernel(const void* __
   __shared__ d2 lds_sa[kGnBlock / kWave][kStashCap];                     // 6 KB: its state,
   __shared__ d2 lds_sp[kGnBlock / kWave][kStashCap];                     // 6 KB: the state before,
   __shared__ double lds_srad[kGnBlock / kWave][kStashCap];               // 3 KB: its acceptance radius  (38 KB: 4 workgroups per CU)
+  if (gn_queue_used_up(counters, tl.n_tiles)) return;                    // (the dedup route's launch without work)
   // the loop of exptab::fill_pow_table, kept as text: the call compiles to another instruction order (tools/device_asm_diff.py)
   for (int j = threadIdx.x; j < kPowN; j += kGnBlock) lds_pow[j] = pow_entry(j);
   __syncthreads();                        // the only barrier: waves work independently from here on
@@ -1886,7 +1971,7 @@ static int gn_decompose_run(const void* g1, const void* g2, int32_t g_is_f64, in
   const double* start = (pass == DEXCT_GN_PASS_SHORTCUT) ? options->start : nullptr;
   hipStream_t st = as_stream(stream);
   double* ws = reinterpret_cast<double*>(workspace);
-  hipLaunchKernelGGL(gn_tables_kernel, dim3(n_bins), dim3(256), 0, st, i0, mus, n_energies, n_bins, ws);
+  hipLaunchKernelGGL(gn_tables_kernel, dim3(n_bins), dim3(kTabBlock), 0, st, i0, mus, n_energies, n_bins, ws);
   DEXCT_LAUNCH_CHECK();
   const GnEnv& env = gn_env();
   // DEXCT_GN_FLAG_FULL_LOOP (or DEXCT_GN_FULL_LOOP=1 at process start) runs every iteration: the check that the repeated-state

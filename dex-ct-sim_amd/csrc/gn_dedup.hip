@@ -98,6 +98,72 @@ __global__ __launch_bounds__(kBlock) void gn_dedup_census_kernel(const B* __rest
   }
 }
 
+// The census of float32 counts whose lines are whole 16-byte pieces (rows a multiple of 4, both sinograms aligned to 16 bytes;
+// census_is_wide).  A lane loads FOUR rows of each sinogram in one piece, a wave 256 rows of a line = four bit words, and two
+// such chunks are loaded before the first is looked at: 4 KB of distinct bytes in flight per wave where fresh_ballot has 1 KB,
+// half of it the neighbour's (profiles/gn_route_streaming.md).  The row before a lane's first comes from the lane below (the
+// chunk before: from its last lane), the comparison is the bit patterns' as in fresh_ballot, and a lane's four bits - its
+// nibble - are OR-ed over the 16 lanes of a DPP row into the row's word: over quads, over half rows, and the upper half row's
+// 32 bits into the lower's.
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+constexpr int kWideRows = 4, kWideChunkWords = kWave * kWideRows / kWordBits, kWideUnroll = 2;
+constexpr int kDppQuadSwap1 = 0xB1, kDppQuadSwap2 = 0x4E, kDppRowHalfMirror = 0x141, kDppRowMirror = 0x140;
+
+__host__ __device__ inline bool census_is_wide(const void* g1, const void* g2, int rows, bool f64) {
+  return !f64 && rows % kWideRows == 0 && (reinterpret_cast<uintptr_t>(g1) & 15u) == 0 && (reinterpret_cast<uintptr_t>(g2) & 15u) == 0;
+}
+
+template <int CTRL>
+__device__ __forceinline__ uint32_t or_dpp(uint32_t x) {
+  return x | (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xF, 0xF, false);
+}
+
+__global__ __launch_bounds__(kBlock) void gn_dedup_census_wide_kernel(const uint32_t* __restrict__ g1, const uint32_t* __restrict__ g2,
+                                                                       long long n_lines, int rows, const unsigned long long* __restrict__ desc,
+                                                                       unsigned long long* __restrict__ bits, unsigned* __restrict__ counts) {
+  if (desc[kDescUse] == 0ull) return;
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, n_words = words_per_line(rows);
+  const int n_quads = rows / kWideRows, n_chunks = (n_quads + kWave - 1) / kWave;
+  for (long long line = (long long)blockIdx.x * kWavesPerBlock + wv; line < n_lines; line += (long long)gridDim.x * kWavesPerBlock) {
+    const u32x4* __restrict__ q1 = reinterpret_cast<const u32x4*>(g1 + line * rows);
+    const u32x4* __restrict__ q2 = reinterpret_cast<const u32x4*>(g2 + line * rows);
+    unsigned cnt = 0u;                                   // (lanes 0, 16, 32, 48: the fresh pixels of their words)
+    uint32_t last1 = 0u, last2 = 0u;                     // the last row of the chunk before
+    for (int j0 = 0; j0 < n_chunks; j0 += kWideUnroll) {
+      u32x4 x1[kWideUnroll], x2[kWideUnroll];
+#pragma unroll
+      for (int u = 0; u < kWideUnroll; ++u) {            // (unconditional: a piece beyond the line reads the line's last)
+        const int q = (j0 + u) * kWave + lane, qc = q < n_quads ? q : n_quads - 1;
+        x1[u] = q1[qc];
+        x2[u] = q2[qc];
+      }
+#pragma unroll
+      for (int u = 0; u < kWideUnroll; ++u) {
+        const int q = (j0 + u) * kWave + lane;
+        uint32_t p1 = (uint32_t)__shfl_up((int)x1[u].w, 1), p2 = (uint32_t)__shfl_up((int)x2[u].w, 1);
+        if (lane == 0) { p1 = last1; p2 = last2; }
+        last1 = (uint32_t)__builtin_amdgcn_readlane((int)x1[u].w, kWave - 1);
+        last2 = (uint32_t)__builtin_amdgcn_readlane((int)x2[u].w, kWave - 1);
+        uint32_t nibble = (q == 0 || x1[u].x != p1 || x2[u].x != p2 ? 1u : 0u) | (x1[u].y != x1[u].x || x2[u].y != x2[u].x ? 2u : 0u) |
+                          (x1[u].z != x1[u].y || x2[u].z != x2[u].y ? 4u : 0u) | (x1[u].w != x1[u].z || x2[u].w != x2[u].z ? 8u : 0u);
+        if (q >= n_quads) nibble = 0u;
+        uint32_t half = nibble << (kWideRows * (lane & 7));
+        half = or_dpp<kDppRowHalfMirror>(or_dpp<kDppQuadSwap2>(or_dpp<kDppQuadSwap1>(half)));
+        const uint32_t upper = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)half, kDppRowMirror, 0xF, 0xF, false);
+        const unsigned long long word = ((unsigned long long)upper << 32) | half;
+        const int k = (j0 + u) * kWideChunkWords + (lane >> 4);
+        if ((lane & 15) == 0 && k < n_words) {
+          bits[word_index(line, rows, k)] = word;
+          cnt += (unsigned)__popcll(word);
+        }
+      }
+    }
+    cnt = (unsigned)(__builtin_amdgcn_readlane((int)cnt, 0) + __builtin_amdgcn_readlane((int)cnt, 16) + __builtin_amdgcn_readlane((int)cnt, 32) +
+                     __builtin_amdgcn_readlane((int)cnt, 48));
+    if (lane == 0) counts[line] = cnt;
+  }
+}
+
 // exclusive scan of one value per thread over a block of N threads (s: N words of LDS); *total: the block's sum
 template <int N>
 __device__ __forceinline__ unsigned block_exclusive_scan(unsigned v, unsigned* s, unsigned* total) {
@@ -337,8 +403,12 @@ int prepare(const GnDedupCall& dc, const void* g1v, const void* g2v, hipStream_t
   hipLaunchKernelGGL(gn_dedup_probe_kernel<B>, dim3((unsigned)(probe_blocks > kProbeMaxGrid ? kProbeMaxGrid : probe_blocks)), dim3(kBlock), 0, st,
                      g1, g2, n_sampled, dc.rows, (long long)y.cap, desc);
   DEXCT_LAUNCH_CHECK();
-  hipLaunchKernelGGL(gn_dedup_census_kernel<B>, dim3(capped_grid(line_blocks)), dim3(kBlock), 0, st, g1, g2, (long long)y.n_lines, dc.rows,
-                     (const unsigned long long*)desc, bits, counts);
+  if (census_is_wide(g1v, g2v, dc.rows, sizeof(B) == 8))
+    hipLaunchKernelGGL(gn_dedup_census_wide_kernel, dim3(capped_grid(line_blocks)), dim3(kBlock), 0, st, reinterpret_cast<const uint32_t*>(g1v),
+                       reinterpret_cast<const uint32_t*>(g2v), (long long)y.n_lines, dc.rows, (const unsigned long long*)desc, bits, counts);
+  else
+    hipLaunchKernelGGL(gn_dedup_census_kernel<B>, dim3(capped_grid(line_blocks)), dim3(kBlock), 0, st, g1, g2, (long long)y.n_lines, dc.rows,
+                       (const unsigned long long*)desc, bits, counts);
   DEXCT_LAUNCH_CHECK();
   const long long n_blocks = scan_blocks(y.n_lines);
   hipLaunchKernelGGL(gn_dedup_sums_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, st, (const unsigned*)counts, (long long)y.n_lines,
