@@ -33,6 +33,84 @@ def to_dev(a, dtype, dev):
     return torch.from_numpy(np.ascontiguousarray(a)).to(device=dev, dtype=dtype)
 
 
+# ---- the tensor contract of the device entry points ------------------------------------------------------------------------------
+# The library reads ``numel`` dense elements of the dtype it assumes from ``t.data_ptr()``, whatever strides and dtype the tensor
+# has.  So every tensor argument of a device entry point passes one of the four functions below before the library is asked for a
+# symbol and before anything is allocated: inputs come back dense and of an accepted dtype (the SAME object when they already
+# are: no copy, no allocation, no synchronisation), written tensors and everything in the wrong memory are refused with a
+# ValueError that names the argument.  Pure functions of the tensor's metadata; ``dev`` may be the CPU (tests).
+GPU = torch.device('cuda')      # what counts as device memory (any index); the CPU tests put a stand-in device type here
+
+
+def _on(t, dev):
+    """The one predicate of this contract: is ``t`` a tensor on ``dev`` (an index that either side leaves open matches)."""
+    dev = torch.device(dev)
+    return (isinstance(t, torch.Tensor) and t.device.type == dev.type
+            and (dev.index is None or t.device.index is None or t.device.index == dev.index))
+
+
+def on_gpu(t):
+    """Is ``t`` a tensor in GPU memory."""
+    return _on(t, GPU)
+
+
+def gpu_of(t, name):
+    """The device of ``t``, which must be a tensor on a GPU (the first tensor of a call says where the call runs)."""
+    if not on_gpu(t):
+        raise ValueError(f'{name} must be a device tensor (got {_where(t)})')
+    return t.device
+
+
+def _where(t):
+    return f'a tensor on {t.device}' if isinstance(t, torch.Tensor) else type(t).__name__
+
+
+def dense_input(t, name, dev, keep=(torch.float32,), cast=None):
+    """A read-only input as the kernels read it: on ``dev`` (else ValueError), of a dtype in ``keep`` - any other dtype is cast
+    to ``cast``, or refused when ``cast`` is None - and dense (a strided, broadcast or transposed view is copied; a dense view
+    at any offset is not).  A tensor that conforms is returned as it is."""
+    if not _on(t, dev):
+        raise ValueError(f'{name} must be a tensor on {torch.device(dev)} (got {_where(t)})')
+    if t.dtype not in keep:
+        if cast is None:
+            raise ValueError(f'{name} must be {" or ".join(str(k).replace("torch.", "") for k in keep)} (got {str(t.dtype).replace("torch.", "")})')
+        t = t.to(cast)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def written(t, name, dev, dtype, numel, at_least=False, align=0):
+    """A tensor the library writes (``out``, a workspace): never normalised - a copy would swallow the result - so it must be on
+    ``dev``, of ``dtype``, dense and of ``numel`` elements (``at_least``: or more) and, where the library stores wider pieces than
+    an element, start on an ``align``-byte boundary; else ValueError.  Returns ``t``."""
+    kind = str(dtype).replace('torch.', '')
+    if not _on(t, dev):
+        raise ValueError(f'{name} must be a tensor on {torch.device(dev)} (got {_where(t)})')
+    if t.dtype != dtype:
+        raise ValueError(f'{name} must be {kind} (got {str(t.dtype).replace("torch.", "")})')
+    if not t.is_contiguous():
+        raise ValueError(f'{name} must be contiguous (got shape {tuple(t.shape)} with strides {tuple(t.stride())})')
+    if t.numel() < int(numel) if at_least else t.numel() != int(numel):
+        raise ValueError(f'{name} must hold {"at least " if at_least else ""}{int(numel)} {kind} elements (got {t.numel()})')
+    if align and t.numel() and t.data_ptr() % align:
+        raise ValueError(f'{name} must start on a {align}-byte boundary (its data starts {t.data_ptr() % align} bytes past one)')
+    return t
+
+
+def device_scalar(t, name, dev):
+    """A scalar the kernels read from device memory as 8 bytes (``mask_max``): one element on ``dev``, float64 - a float32 one
+    is cast, any other dtype or element count is refused.  A conforming one is returned as it is."""
+    if not _on(t, dev):
+        raise ValueError(f'{name} must be a one-element float64 tensor on {torch.device(dev)} (got {_where(t)})')
+    if t.numel() != 1:
+        raise ValueError(f'{name} must hold one element (got {t.numel()})')
+    if t.dtype not in (torch.float32, torch.float64):
+        raise ValueError(f'{name} must be float64 (got {str(t.dtype).replace("torch.", "")})')
+    return t if t.dtype == torch.float64 else t.to(torch.float64)
+
+
+COUNTS = dict(keep=(torch.float32, torch.float64), cast=torch.float64)       # counts: float32 and float64 stay, anything else -> float64
+
+
 def to_host(t):
     """Device tensor -> NumPy array through PAGE-LOCKED host memory (one DMA at PCIe rate instead of a staged copy
     through pageable memory).  The pinned buffer comes from torch's caching host allocator and is referenced by the

@@ -14,8 +14,8 @@ input/params.txt:24) down to pi + the fan angle are reconstructed with Parker's 
 import numpy as np
 import torch
 
-from . import _native, iterative, xcompy
-from ._device import device, ptr, stream_ptr, to_dev, to_host
+from . import _device, _native, iterative, xcompy
+from ._device import dense_input, device, gpu_of, ptr, stream_ptr, to_dev, to_host
 from .forward_project import effective_weights
 
 WATER = 'H(11.2)O(88.8)'       # the composition plots.py:140 uses for HU
@@ -177,8 +177,13 @@ def recon_device(sino_d, ct, N_matrix, FOV, ramp, window=None, slices=None, bhc=
     [N_matrix, N_matrix] or [N_rows, N_matrix, N_matrix] (float32, 1/cm).  A cone-beam scanner (``ct.cone``) is
     reconstructed with Feldkamp's algorithm onto ``slices = (n_slices, z_first [cm], dz [cm])``.  ``bhc``: a
     ``bhc.LinearizationTable`` - the sinogram is linearised first (into a new buffer; sino_d is left as it is), before
-    Parker's weights, which a nonlinear map must not follow.  ``method`` and the keywords after it: see get_recon."""
+    Parker's weights, which a nonlinear map must not follow.  ``method`` and the keywords after it: see get_recon.
+    Tensor contract: any view or dtype of ``sino_d`` is made dense float32 first; a host tensor is refused."""
     n_subsets = iterative.check_options(method, ct, n_iters, n_subsets, relax, init)
+    # the tensor contract (_device.py): the kernels read dense float32 - a view is made dense, another dtype (the float64
+    # stride-2 views get_basismat_sinos hands out) is cast as get_recon casts host arrays, a host tensor is refused
+    sino_d = dense_input(sino_d, 'sino_d', gpu_of(sino_d, 'sino_d'), keep=(torch.float32,), cast=torch.float32)
+    _check_sino_shape(sino_d.shape, ct)
     if method != 'fbp':
         return _recon_sirt(sino_d, ct, N_matrix, FOV, ramp, window, bhc, n_iters, n_subsets, relax, init, nonneg, history)
     lib = _native.load()
@@ -187,7 +192,6 @@ def recon_device(sino_d, ct, N_matrix, FOV, ramp, window=None, slices=None, bhc=
         from .bhc import linearize_device
         s = linearize_device(s, bhc)
     n_views, n_rows, n_ch = s.shape
-    _check_sino_shape(sino_d.shape, ct)
     st = stream_ptr()
     if _short_scan(ct):
         sw = torch.empty_like(s)
@@ -371,9 +375,10 @@ def recon_covariance_device(cov_d, ct, N_matrix, FOV, ramp, window=None, slices=
     ``window`` and ``slices`` (Parker weights of a short scan and Feldkamp's cone branch included): the element-wise square of
     the FBP matrix applied to every plane (dexct_fbp_var_filter, dexct_fbp_var_backproject, dexct_fdk_var_backproject).  The
     result is pixel-wise: neighbouring image pixels are correlated, the variance of an ROI mean is not its average."""
-    if not isinstance(cov_d, torch.Tensor) or not cov_d.is_cuda or cov_d.dtype != torch.float64:
+    if not _device.on_gpu(cov_d) or cov_d.dtype != torch.float64:
         raise ValueError('cov_d must be a float64 device tensor')
     window = _check_cov_sino(cov_d.shape, ct, window)
+    cov_d = dense_input(cov_d, 'cov_d', cov_d.device, keep=(torch.float64,))
     lib = _native.load()
     s, back = _stack(cov_d, tail=1)
     n_views, n_rows, n_ch, n_planes = s.shape

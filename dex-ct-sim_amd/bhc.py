@@ -37,7 +37,7 @@ import os
 import numpy as np
 import torch
 
-from . import _native, xcompy
+from . import _device, _native, xcompy
 from ._device import ptr, stream_ptr
 from .forward_project import effective_weights
 
@@ -268,12 +268,13 @@ def linearize(sino_log, ct, spec, material='water', mu_ref=None):
 def linearize_device(sino_d, table, out=None):
     """dexct_bhc_linearize on a float32 device tensor of any shape (contiguous; a view at any offset is fine).
     ``out``: a contiguous float32 tensor of the same shape, ``sino_d`` itself for in place, or None for a new one."""
-    if sino_d.dtype != torch.float32 or not sino_d.is_cuda or not sino_d.is_contiguous():
+    if not _device.on_gpu(sino_d) or sino_d.dtype != torch.float32 or not sino_d.is_contiguous():
         raise ValueError('linearize_device needs a contiguous float32 device tensor')
+    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != sino_d.shape
+                            or not out.is_contiguous() or out.device != sino_d.device):
+        raise ValueError("out must be a contiguous float32 tensor of the input's shape and device")
     if out is None:
         out = torch.empty_like(sino_d, memory_format=torch.contiguous_format)
-    elif out.dtype != torch.float32 or out.shape != sino_d.shape or not out.is_contiguous() or out.device != sino_d.device:
-        raise ValueError("out must be a contiguous float32 tensor of the input's shape and device")
     lib = _native.load()
     tab = table.device(sino_d.device)
     _native.check(lib.dexct_bhc_linearize(ptr(sino_d), sino_d.numel(), ptr(tab), table.log2_min, table.cells_log2,

@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _native, _shard
-from ._device import LazyPinnedResult, device, pinned_empty, pool_wanted, ptr, side_streams, stream_ptr, to_dev
+from ._device import LazyPinnedResult, dense_input, device, pinned_empty, pool_wanted, ptr, side_streams, stream_ptr, to_dev, written
 
 
 def effective_weights(ct, spec):
@@ -344,7 +344,9 @@ class Projector:
         same store.  The other kernels write the variance and dexct_add_noise draws the same sample from it.
         ``want_variance``: the variance of the detected signal as a further result (appended last; tests).
         ``views=(a, b)``: only the local views [a, b) of this projector's range (outputs sized for b - a views): a step that
-        hands its sinogram on in chunks projects chunk by chunk (bench.py, the sharded step)."""
+        hands its sinogram on in chunks projects chunk by chunk (bench.py, the sharded step).
+        Tensor contract: the tables in any layout on the projector's device (made dense float32); ``out`` and
+        ``log_out`` dense float32 device tensors of the layout's element count, else ValueError."""
         # ---- 1. the tables and the view range
         mu_d, w_d, w2_d, sl0, sl1 = self._check_tables(mu_d, w_d, w2_d, views)
         S, nE = w_d.shape
@@ -356,6 +358,10 @@ class Projector:
         shape = {0: (S, nV, nR, nC), 1: (S, nV, nC, nR)}
         direct = want == native or nR == 1
         run_layout = want if direct else native
+        # written tensors are never normalised (_device.written): right device, float32, dense and of the layout's size, or refused
+        for name, t in (('out', out), ('log_out', log_out)):
+            if t is not None:
+                written(t, name, self.dev, torch.float32, S * nV * nR * nC)
         # the log sinogram: written by the detection store when the kernel's layout is the one wanted; else together with the
         # transpose at the end (dexct_transpose_log: the counts are read once for both outputs)
         fuse_log = air is not None and not direct
@@ -401,10 +407,13 @@ class Projector:
 
     def _check_tables(self, mu_d, w_d, w2_d, views):
         """project_tables' tables as the kernels read them, mu with the rows of the compact ids, and the local view range."""
-        # the kernels read the tables through raw pointers: dense float32, whatever view the caller built
-        # (torch.tensor(w[:, keep]) keeps NumPy's column-major result of the advanced index)
-        mu_d, w_d = (t.to(dtype=torch.float32).contiguous() for t in (mu_d, w_d))
-        w2_d = None if w2_d is None else w2_d.to(dtype=torch.float32).contiguous()
+        # the kernels read the tables through raw pointers: dense float32 on the projector's device, whatever view the caller
+        # built (torch.tensor(w[:, keep]) keeps NumPy's column-major result of the advanced index); a host tensor is refused
+        f32 = dict(keep=(torch.float32,), cast=torch.float32)
+        mu_d, w_d = dense_input(mu_d, 'mu_d', self.dev, **f32), dense_input(w_d, 'w_d', self.dev, **f32)
+        w2_d = None if w2_d is None else dense_input(w2_d, 'w2_d', self.dev, **f32)
+        if mu_d.dim() != 2 or w_d.dim() != 2:
+            raise ValueError(f'tables must be [rows, nE]: mu {tuple(mu_d.shape)}, w {tuple(w_d.shape)}')
         S, nE = w_d.shape
         if mu_d.shape[1] != nE or (w2_d is not None and tuple(w2_d.shape) != (S, nE)):
             raise ValueError(f'tables disagree: mu {tuple(mu_d.shape)}, w {tuple(w_d.shape)}' + ('' if w2_d is None else f', w2 {tuple(w2_d.shape)}'))
@@ -495,16 +504,24 @@ class Projector:
 
     def transpose_log(self, src, dst, log_dst, air, rows, cols):
         """src [S, n, rows, cols] -> dst [S, n, cols, rows] and (``log_dst`` not None) ln(air[s] / dst[s]) in the same pass
-        (dexct_transpose_log)."""
+        (dexct_transpose_log).  ``src`` in any layout; ``dst`` and ``log_dst`` dense float32 of src's element count, else ValueError."""
+        src = dense_input(src, 'src', self.dev, keep=(torch.float32,), cast=torch.float32)
+        if src.dim() != 4 or tuple(src.shape[2:]) != (int(rows), int(cols)):
+            raise ValueError(f'src must be [S, n, {rows}, {cols}], got {tuple(src.shape)}')
         S, n = int(src.shape[0]), int(src.shape[1])
+        written(dst, 'dst', self.dev, torch.float32, src.numel())
+        if log_dst is not None:
+            written(log_dst, 'log_dst', self.dev, torch.float32, src.numel())
         arr = self._air_array(air, S) if log_dst is not None else None
         _native.check(self.lib.dexct_transpose_log(ptr(src), ptr(dst), ptr(log_dst), arr, S, n, rows, cols, stream_ptr()),
                       'dexct_transpose_log')
 
     def sino_log(self, counts, air, out=None):
-        """ln(air[s] / counts[s]) as a pass of its own (dexct_sino_log): noisy and gathered sinograms."""
+        """ln(air[s] / counts[s]) as a pass of its own (dexct_sino_log): noisy and gathered sinograms.  ``counts`` in any layout;
+        ``out`` a dense float32 device tensor of its element count, else ValueError."""
+        counts = dense_input(counts, 'counts', self.dev, keep=(torch.float32,), cast=torch.float32)
         S = counts.shape[0]
-        out = torch.empty_like(counts) if out is None else out
+        out = torch.empty_like(counts) if out is None else written(out, 'out', self.dev, torch.float32, counts.numel())
         _native.check(self.lib.dexct_sino_log(ptr(counts), self._air_array(air, S), S, counts[0].numel(), ptr(out), stream_ptr()),
                       'dexct_sino_log')
         return out

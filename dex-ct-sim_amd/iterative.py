@@ -32,8 +32,8 @@ import weakref
 import numpy as np
 import torch
 
-from . import _native
-from ._device import device, ptr, stream_ptr, to_dev
+from . import _device, _native
+from ._device import dense_input, device, ptr, stream_ptr, to_dev
 
 METHODS = ('fbp', 'sirt', 'os-sart')
 OS_SART_SUBSETS = 10
@@ -143,7 +143,9 @@ class ImageProjector:
         return begin, end, step
 
     def _tensor(self, t, shape, what):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+        """The tensor contract of this module (_device.py): strict - nothing is normalised; every argument is checked on the
+        host before the projector's device state is built."""
+        if not (_device.on_gpu(t) and t.dtype == torch.float32 and t.is_contiguous()):
             raise ValueError(f'{what}: a contiguous float32 device tensor wanted')
         if t.numel() != int(np.prod(shape)):
             raise ValueError(f'{what}: shape {tuple(t.shape)} does not match {shape}')
@@ -152,12 +154,14 @@ class ImageProjector:
     def forward(self, img_d, views=None, out=None):
         """A x: image [nz, ny, nx] ([ny, nx] for one slice) -> sinogram [n_views, n_rows, n_channels].  ``views = (begin, end,
         step)``: only those views are computed; the other lines of ``out`` stay (zeros in a new tensor)."""
-        self._ready()
         begin, end, step = self._views(views)
         img = self._tensor(img_d, self.image_shape, 'image')
+        if out is not None:
+            self._tensor(out, self.sino_shape, 'out')
+        self._ready()
         if out is None:
             out = torch.zeros(self.sino_shape, dtype=torch.float32, device=self.dev)
-        sino = self._tensor(out, self.sino_shape, 'out')
+        sino = out
         st = stream_ptr()
         if self.transposed:
             _native.check(self.lib.dexct_transpose_batched(ptr(img), ptr(self.scratch), self.nz, self.ny, self.nx, 4, st),
@@ -170,13 +174,15 @@ class ImageProjector:
 
     def adjoint(self, sino_d, views=None, out=None, accumulate=False):
         """A^T y over the views -> image [nz, ny, nx]; ``out`` is overwritten unless ``accumulate``."""
-        self._ready()
         begin, end, step = self._views(views)
         sino = self._tensor(sino_d, self.sino_shape, 'sinogram')
+        if out is not None:
+            self._tensor(out, self.image_shape, 'out')
+        self._ready()
         if out is None:
             out = torch.empty(self.image_shape, dtype=torch.float32, device=self.dev)
             accumulate = False
-        img = self._tensor(out, self.image_shape, 'out')
+        img = out
         line = self.n_rows * self.n_channels
         _native.check(self.lib.dexct_image_backproject(
             C.byref(self.geom), self.plan.data_ptr() + begin * self.n_channels * _native.PLAN_BYTES, begin, end, step,
@@ -216,11 +222,12 @@ def sirt(sino_d, proj, n_iters, n_subsets=1, relax=1.0, x0=None, nonneg=True, hi
     if n_iters < 1 or not 1 <= S <= proj.n_views or not 0.0 < relax < 2.0:
         raise ValueError(f'n_iters = {n_iters}, n_subsets = {S}, relax = {relax}: n_iters >= 1, 1 <= n_subsets <= '
                          f'{proj.n_views} and 0 < relax < 2 wanted')
+    b = proj._tensor(sino_d, proj.sino_shape, 'sinogram')
+    if x0 is not None:
+        proj._tensor(x0, proj.image_shape, 'x0')
     proj._ready()
     lib, dev = proj.lib, proj.dev
-    b = proj._tensor(sino_d, proj.sino_shape, 'sinogram')
-    x = torch.zeros(proj.image_shape, dtype=torch.float32, device=dev) if x0 is None else \
-        proj._tensor(x0, proj.image_shape, 'x0').clone()
+    x = torch.zeros(proj.image_shape, dtype=torch.float32, device=dev) if x0 is None else x0.clone()
     R = proj.row_sums()
     ax = torch.zeros(proj.sino_shape, dtype=torch.float32, device=dev)
     g = torch.empty(proj.image_shape, dtype=torch.float32, device=dev)
@@ -295,12 +302,12 @@ def precision_weights(cov_d, w_fill=0.0):
     matdecomp.gn_covariance_device) -> float32 [T, ...], plane-major, each plane a sinogram (dexct_cov_precision: the float64
     closed-form inverse rounded once; a ray whose matrix is not finite and positive definite gets ``w_fill`` on the diagonal
     planes and 0 elsewhere)."""
-    if not (isinstance(cov_d, torch.Tensor) and cov_d.is_cuda and cov_d.dtype == torch.float64):
+    if not (_device.on_gpu(cov_d) and cov_d.dtype == torch.float64):
         raise ValueError('cov_d must be a float64 device tensor')
     T = cov_d.shape[-1]
     K = channels_of(T)
     check_w_fill(w_fill)
-    c = cov_d.contiguous()
+    c = dense_input(cov_d, 'cov_d', cov_d.device, keep=(torch.float64,))
     w = torch.empty((T,) + tuple(c.shape[:-1]), dtype=torch.float32, device=c.device)
     _native.check(_native.load().dexct_cov_precision(ptr(c), c.numel() // T, K, float(w_fill), ptr(w), stream_ptr()),
                   'dexct_cov_precision')
@@ -355,12 +362,13 @@ def pwls(sinos_d, weights_d, proj, n_iters, n_subsets=1, beta=0.0, delta=1e-3, x
         raise ValueError(f'sinograms {tuple(sinos_d.shape)}: [K, n_views, n_rows, n_channels] with K = 1 .. {PWLS_MAX_CHANNELS} wanted')
     T = K * (K + 1) // 2
     betas, deltas = per_channel(beta, K, 'beta'), per_channel(delta, K, 'delta', positive=True)
-    proj._ready()
-    lib, dev = proj.lib, proj.dev
     b = proj._tensor(sinos_d, (K,) + proj.sino_shape, 'sinograms')
     w = proj._tensor(weights_d, (T,) + proj.sino_shape, 'weights')
-    x = torch.zeros((K,) + proj.image_shape, dtype=torch.float32, device=dev) if x0 is None else \
-        proj._tensor(x0, (K,) + proj.image_shape, 'x0').clone()
+    if x0 is not None:
+        proj._tensor(x0, (K,) + proj.image_shape, 'x0')
+    proj._ready()
+    lib, dev = proj.lib, proj.dev
+    x = torch.zeros((K,) + proj.image_shape, dtype=torch.float32, device=dev) if x0 is None else x0.clone()
     y = torch.empty_like(x)
     R = proj.row_sums()
     d = _pwls_majoriser(proj, w, K)

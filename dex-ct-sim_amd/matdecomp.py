@@ -23,7 +23,8 @@ import numpy as np
 import torch
 
 from . import _native, _shard, xcompy as xc
-from ._device import LazyPinnedResult, device, locked_arrays, pinned_empty, pool_wanted, side_streams, ptr, stream_ptr, to_dev, to_host
+from ._device import (COUNTS, LazyPinnedResult, dense_input, device, device_scalar, gpu_of, locked_arrays, pinned_empty, pool_wanted,
+                      side_streams, ptr, stream_ptr, to_dev, to_host, written)
 
 # Basis materials, as data (matdecomp.py:11-17).
 mat1 = 'ICRU tissue'
@@ -517,7 +518,9 @@ def gn_device(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=N
     and can pay: rows >= DEDUP_MIN_ROWS and DEDUP_MIN_PIXELS pixels; True: wherever the library accepts a dedup workspace;
     False: never.  last_gn_stats()['dedup'] says what the device then decided.  ``dedup_workspace``: a uint8 device tensor of at
     least dexct_gn_dedup_workspace_bytes bytes to use for it (default: a new one; tests pass guarded, pre-filled ones).
-    Returns a device tensor of shape g1.shape + (2,) float64 (with ``out_rc``: the last two sinogram dimensions swapped)."""
+    Returns a device tensor of shape g1.shape + (2,) float64 (with ``out_rc``: the last two sinogram dimensions swapped).
+    Tensor contract: g1, g2, tables and ``mask_max`` in any layout (made dense; float32 / float64 counts kept, other
+    dtypes -> float64; a float32 ``mask_max`` cast); ``out``: float64, dense, two values per pixel, on a 16-byte boundary, else ValueError."""
     global _last_run
     a, ws, ev, zeroed, mode, n_e, dws = _gn_launch(g1, g2, i0, mus, n_iters, precision, n_polish, out, bin_div, mask_max, mask_frac,
                                                    stop_tol, out_rc, kernel, two_level, full_loop, natural_order, blocks_per_cu, reduced,
@@ -541,13 +544,18 @@ def _gn_launch(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=
     """One dexct_gn_decompose (or dexct_gn_decompose_dedup) launch with gn_device's arguments (see there): everything up to and
     including the call.  Touches no module state.  Returns (result, workspace, (before, after) events, the event recorded after
     the counters were zeroed, mode, n_e, the dedup workspace or None)."""
-    lib = _native.load()
-    dev = g1.device
+    # the tensor contract (_device.py): every refusal on the host, before the library or the device is touched
+    dev = gpu_of(g1, 'g1')
+    if isinstance(g2, torch.Tensor) and (g1.shape != g2.shape or g1.dtype != g2.dtype):
+        raise ValueError('the two sinograms must agree in shape and dtype')
+    g1, g2 = dense_input(g1, 'g1', dev, **COUNTS), dense_input(g2, 'g2', dev, **COUNTS)
+    if mask_max is not None:
+        mask_max = device_scalar(mask_max, 'mask_max', dev)
+    if dedup_workspace is not None:
+        written(dedup_workspace, 'dedup_workspace', dev, torch.uint8, 0, at_least=True, align=16)
     precision = precision or DEFAULT_PRECISION
     if precision not in ('f64', 'mixed'):
         raise ValueError(f'precision {precision!r}')
-    if g1.shape != g2.shape or g1.dtype != g2.dtype:
-        raise ValueError('the two sinograms must agree in shape and dtype')
     explicit_tol = stop_tol is not None
     if stop_tol is None:
         stop_tol = DEFAULT_STOP_TOL
@@ -571,6 +579,16 @@ def _gn_launch(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=
     applies = (precision == 'f64' and n_bins == 1 and kernel != 2 and 4 <= int(n_iters) <= 254 and n_e >= 48 and stop_tol > 0.0)
     # (the gate is consulted for the default tolerance even with two_level=False: an ill-posed pair runs the fixed count)
     want_gate = applies and (bool(two_level) or not explicit_tol)
+    shape = tuple(g1.shape)
+    rows = chans = 0
+    if out_rc is not None:
+        rows, chans = int(out_rc[0]), int(out_rc[1])
+        if shape[-2:] != (chans, rows):
+            raise ValueError(f'out_rc={out_rc}: the sinograms must end in [channel={chans}, row={rows}], got {shape}')
+        shape = shape[:-2] + (rows, chans)
+    if out is not None:
+        written(out, 'out', dev, torch.float64, 2 * g1.numel(), align=16)      # (a pixel's two doubles leave as one 16-byte store)
+    lib = _native.load()
     i0_d, mus_d, gate = _device_tables(i0, mus, dev, want_gate, min(stop_tol, 1.0e-12) or 1.0e-12)
     start = None
     mode = 'single'
@@ -579,16 +597,7 @@ def _gn_launch(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=
             stop_tol, mode = 0.0, 'exact (ill-posed pair)'
         elif two_level and gate['start'] is not None:
             start, mode = gate['start'], (two_level if gate['stats'].get('one_step_share', 0.0) > 0.0 else 'start')
-    shape = tuple(g1.shape)
-    rows = chans = 0
-    if out_rc is not None:
-        rows, chans = int(out_rc[0]), int(out_rc[1])
-        if shape[-2:] != (chans, rows):
-            raise ValueError(f'out_rc={out_rc}: the sinograms must end in [channel={chans}, row={rows}], got {shape}')
-        shape = shape[:-2] + (rows, chans)
     a = out if out is not None else torch.empty(shape + (2,), dtype=torch.float64, device=dev)
-    if out is not None and (a.numel() != 2 * g1.numel() or a.dtype != torch.float64 or not a.is_contiguous()):
-        raise ValueError('out must be a contiguous float64 tensor with two values per pixel')
     is64 = int(g1.dtype == torch.float64)
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     ws = torch.empty(lib.dexct_gn_workspace_bytes(n_e, n_bins), dtype=torch.uint8, device=dev)
@@ -615,8 +624,8 @@ def _gn_launch(g1, g2, i0, mus, n_iters, precision=None, n_polish=N_POLISH, out=
     if dedup and route:
         need = lib.dexct_gn_dedup_workspace_bytes(n_pix, rows, is64)
         dws = dedup_workspace if dedup_workspace is not None else torch.empty(need, dtype=torch.uint8, device=dev)
-        if dws.dtype != torch.uint8 or dws.numel() < need or not dws.is_contiguous() or dws.device != g1.device:
-            raise ValueError(f'dedup_workspace must be a contiguous uint8 tensor of at least {need} bytes on the sinograms\' device')
+        if dws.numel() < need:          # (the one refusal after the library is loaded: it alone knows the size; the rest was checked above)
+            raise ValueError(f'dedup_workspace must hold at least {need} bytes (got {dws.numel()})')
         dws[:24].zero_()                  # (the descriptor reads 0 / 0 / 0 where the library takes the direct route without a probe)
     args = (ptr(g1), ptr(g2), is64, n_pix, ptr(i0_d), ptr(mus_d), n_e, n_bins, int(bin_div), int(n_iters), int(precision == 'mixed'),
             int(n_polish), ptr(mask_max), float(mask_frac), ptr(a), opts, ptr(ws))
@@ -757,7 +766,8 @@ def gn_device_multi(g, i0, mus, n_iters, mask_max=None, mask_frac=0.95, full_loo
     on the device).  ``mask_max``: device float64 scalar - pixels with g[0] >= mask_frac * max get 0 in every component and
     are not iterated.  ``full_loop``: run every iteration (the default ends a pixel whose update returned its own input bit for
     bit; the results are the same bits).  Returns a device tensor g.shape[1:] + (M,) float64: the state after n_iters
-    iterations of matdecomp.py:114-125."""
+    iterations of matdecomp.py:114-125.  Tensor contract: ``g``, tables and ``mask_max`` are normalised as in
+    gn_device; ``out`` must be a dense float64 device tensor of M values per pixel, else ValueError."""
     if not isinstance(g, torch.Tensor) or g.dim() < 2:
         raise ValueError('g must be a device tensor [nMeas, ...]')
     shp_i0 = tuple(i0.shape) if hasattr(i0, 'shape') else np.shape(i0)
@@ -767,13 +777,13 @@ def gn_device_multi(g, i0, mus, n_iters, mask_max=None, mask_frac=0.95, full_loo
                                               n_iters)
     shape = tuple(g.shape[1:])
     n_pix = int(np.prod(shape))
-    if out is not None and (out.numel() != n_mats * n_pix or out.dtype != torch.float64 or not out.is_contiguous()):
-        raise ValueError(f'out must be a contiguous float64 tensor with {n_mats} values per pixel')
+    dev = gpu_of(g, 'g')
+    g = dense_input(g, 'g', dev, **COUNTS)
+    if mask_max is not None:
+        mask_max = device_scalar(mask_max, 'mask_max', dev)
+    if out is not None:
+        written(out, 'out', dev, torch.float64, n_mats * n_pix)
     lib = _native.load()
-    dev = g.device
-    if g.dtype not in (torch.float32, torch.float64):
-        g = g.to(torch.float64)
-    g = g.contiguous()
     i0_d = to_dev(i0 if isinstance(i0, torch.Tensor) else np.asarray(i0, dtype=np.float64), torch.float64, dev)
     mus_d = to_dev(mus if isinstance(mus, torch.Tensor) else np.asarray(mus, dtype=np.float64), torch.float64, dev)
     a = out if out is not None else torch.empty(shape + (n_mats,), dtype=torch.float64, device=dev)
@@ -1066,7 +1076,8 @@ def gn_covariance_device(a, i0, i0v, mus, kind='estimator', mask_g=None, mask_ma
     (float64), i0 / i0v [K, nE] and mus [M, nE] host arrays or device tensors.  ``kind``: 'estimator' - the delta-method
     covariance of the Poisson-likelihood Newton solve - or 'crlb'.  ``mask_g`` (device tensor of a's pixel shape, float32 or
     float64: the counts of measurement 0) with ``mask_max`` (device float64 scalar): pixels with mask_g >= mask_frac * max get
-    exact zeros.  Returns a device tensor [..., T] float64, T = M (M + 1) / 2: the row-major upper triangle."""
+    exact zeros.  Returns a device tensor [..., T] float64, T = M (M + 1) / 2: the row-major upper triangle.  Tensor contract
+    (INTEGRATION.md): ``a``, ``mask_g``, tables and ``mask_max`` in any layout on a's device; ``out`` dense float64 of T per pixel."""
     kind_id = _cov_kind(kind)
     if not isinstance(a, torch.Tensor) or a.dim() < 1:
         raise ValueError('a must be a device tensor [..., nMats]')
@@ -1084,18 +1095,14 @@ def gn_covariance_device(a, i0, i0v, mus, kind='estimator', mask_g=None, mask_ma
         raise ValueError('mask_g and mask_max go together')
     if mask_g is not None and (not isinstance(mask_g, torch.Tensor) or tuple(mask_g.shape) != shape):
         raise ValueError(f'mask_g must be a device tensor of shape {shape}')
-    if out is not None and (out.numel() != n_tri * n_pix or out.dtype != torch.float64 or not out.is_contiguous()):
-        raise ValueError(f'out must be a contiguous float64 tensor with {n_tri} values per pixel')
-    for name, t in (('a', a), ('mask_g', mask_g), ('mask_max', mask_max), ('out', out)):
-        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != a.device):
-            raise ValueError(f'{name} must be a tensor on the device of a, and that a GPU (got {getattr(t, "device", type(t).__name__)})')
-    lib = _native.load()
-    dev = a.device
-    a = a.to(torch.float64).contiguous()
+    dev = gpu_of(a, 'a')
+    a = dense_input(a, 'a', dev, keep=(torch.float64,), cast=torch.float64)
     if mask_g is not None:
-        if mask_g.dtype not in (torch.float32, torch.float64):
-            mask_g = mask_g.to(torch.float64)
-        mask_g = mask_g.contiguous()
+        mask_g = dense_input(mask_g, 'mask_g', dev, **COUNTS)
+        mask_max = device_scalar(mask_max, 'mask_max', dev)
+    if out is not None:
+        written(out, 'out', dev, torch.float64, n_tri * n_pix)
+    lib = _native.load()
     tab = [to_dev(x if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64), torch.float64, dev) for x in (i0, i0v, mus)]
     cov = out if out is not None else torch.empty(shape + (n_tri,), dtype=torch.float64, device=dev)
     if n_pix == 0:
